@@ -3,10 +3,17 @@
     python bench.py [--gpus N --steps K --warmup W]            # N>1: starts N rank processes itself
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --workload cfg2|cfg5|cfg3ucn               # the other GPU configs (own lines)
+    python bench.py --full                                     # the headline and everything measured beside it
+    python bench.py --dump-outputs DIR                         # the last timed step's outputs as DIR/*.npy
+
+A plain run sets up, warms up, times the K steps, counts the bit errors of the last step's outputs and prints
+the line.  Everything below that is measured beside the headline (side lines, per-kernel HIP-event times and
+roofline, measured HBM ceilings, count-only decode, BER sweep, the reference's BER helper, CPU baseline, cfg2's
+eager timing next to its graph replay) runs with --full only.
 
 Default workload cfg3: a step = one NeuralLDPCDecoder.forward over the rank's batch of B codewords
 (default 65536 per GPU, weak scaling), T=20 iterations, every iteration's posterior written (the
-reference API's output list).  At N=1 the default run also times the other single-GPU BASELINE configs
+reference API's output list).  At N=1 the --full run also times the other single-GPU BASELINE configs
 with the same timed() helper and reports them under `side_lines` (never as `value`): cfg5 and cfg2
 (--no-side-lines skips them).  cfg2: the same decode on WiMAX N=576 R=3/4 z=24, B=4096.  cfg5: one
 BoostedNeuralLDPCDecoder training step (QMS q=5, NW(3,0,3), T=50, B=2048: forward over all
@@ -15,7 +22,7 @@ train/train_BoostedNeuralLDPCDecoder.py:278-294 does it.
 Inputs: synthetic all-zero codewords over BPSK/AWGN at Eb/N0 = 2 dB generated on the device
 (Philox, counter = global codeword index, so N GPUs decode exactly the codewords a single GPU would
 decode at B*N).  Timed region: barrier + synchronize on both sides of K steps, max over ranks.
-After timing: BER/FER of the last iteration summed over ranks with one RCCL all_reduce, and (cfg3)
+After timing: BER/FER of the last iteration summed over ranks with one RCCL all_reduce, and with --full (cfg3)
 a BER sweep over Eb/N0 = 1.0..4.0 dB; on rank 0 at N=1 the CPU oracle (oracle/ldpc_oracle.py, the
 restatement pinned to the reference) is timed on a bounded sample of the same workload as the CPU
 baseline.  Rank 0 prints one JSON line.
@@ -78,7 +85,38 @@ def parse():
     ap.add_argument("--side-steps-cfg2", type=int, default=200, help="timed steps of the cfg2 side line")
     ap.add_argument("--nw", default="1,1,2", help="cfg3ucn: NodeWeightSharingConfig (cn, ucn, vn) codes")
     ap.add_argument("--kind", default="MS", choices=("MS", "QMS", "SP"), help="cfg3ucn: Boosted decoding type")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: HIP-event per-kernel timing and roofline with the "
+                         "measured HBM ceilings, count-only decode, Eb/N0 sweep, reference BER helper, CPU baseline, "
+                         "the cfg5 / cfg2 side lines, cfg2's eager timing (each still has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; "
+                         "a fixed sample of the codewords of a large batch)")
+    args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, (dump the outputs,) print the line
+        args.no_cpu_baseline = args.no_profile = args.no_sweep = args.no_count_only = args.no_side_lines = True
+    return args
+
+
+DUMP_BYTES = 48 << 20  # bound of one --dump-outputs directory (float32 .npy files)
+
+
+def dump_rows(B, row_bytes, seed=2042):
+    """The codewords of a batch of B that --dump-outputs writes: all of them while B * row_bytes fits DUMP_BYTES, else
+    the first, the last and a fixed seeded choice of the others (ascending), the same for every run and build."""
+    n = max(2, DUMP_BYTES // row_bytes)
+    if B <= n:
+        return np.arange(B)
+    mid = 1 + np.random.default_rng(seed).choice(B - 2, size=n - 2, replace=False)
+    return np.sort(np.concatenate([[0, B - 1], mid]))
+
+
+def dump_outputs(path, rank, world, arrays):
+    """Write {name: tensor} as path/<name>.npy in float32 (every rank its own files when there are several)."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
 
 
 def kernel_bytes(B, E, N, Z, T, train=None):
@@ -327,7 +365,7 @@ def side_lines(args, rank, world, local, dev, cus, ceilings):
     for wl, steps, warmup in (("cfg5", args.steps, args.warmup), ("cfg2", args.side_steps_cfg2, 20)):
         a = copy.copy(args)
         a.workload, a.steps, a.warmup = wl, steps, warmup
-        a.batch = a.iters = None
+        a.batch = a.iters = a.dump_outputs = None
         a.no_sweep = a.no_count_only = a.no_cpu_baseline = True
         a.graph = "auto"
         torch.cuda.empty_cache()
@@ -414,7 +452,8 @@ def bench_decode(args, rank, world, local, dev, bg, Z, T, B, cus=256, ceilings=N
     E = int(conn.sum_edge)
     offset, _ = nd_dist.shard(world * B, rank, world)  # weak scaling: rank r holds [r*B, (r+1)*B)
     xa = awgn_llr(B, N, Z, sigma_for(args.ebn0, rate), seed=2042, b_offset=offset, device=dev)
-    xa_host = xa[:min(B, 2048)].cpu()  # the CPU baseline decodes these same Philox codewords
+    # the CPU baseline decodes these same Philox codewords
+    xa_host = xa[:min(B, 2048)].cpu() if (world == 1 and not args.no_cpu_baseline and not ucn) else None
     torch.cuda.synchronize(dev)
     state = {}
 
@@ -424,15 +463,20 @@ def bench_decode(args, rank, world, local, dev, bg, Z, T, B, cus=256, ceilings=N
 
     use_graph = args.graph == "on" or (args.graph == "auto" and args.workload == "cfg2")
     graph_info = None
+    prof = lit_bits = lit_frames = gpu_last = None
     with torch.no_grad():
-        elapsed, prof, step_ms = timed(args, local, dev, step, Prof(not args.no_profile, args.steps * (2 * T + 2)))
+        if args.full or not use_graph:
+            elapsed, prof, step_ms = timed(args, local, dev, step, Prof(not args.no_profile, args.steps * (2 * T + 2)))
+        else:  # a plain graph run times the replays only: one eager call so that nothing is first used under capture
+            step()
+            torch.cuda.synchronize(dev)
         if use_graph:
             # the same module call captured once into a HIP graph (stream capture of the library's launch on
             # torch's stream; outputs in the graph's pool), each step one replay: the host path of a module
             # call (Python, argument checks, ctypes) leaves the timed loop.  The eager timing above gives the
             # per-kernel HIP-event profile (events cannot be recorded inside the graph) and is reported beside.
-            eager = {"ms_per_step": round(1000.0 * nd_dist.max_time(elapsed, device=dev) / args.steps, 3),
-                     "ms_per_step_median": round(statistics.median(step_ms), 3)}
+            eager = ({"ms_per_step": round(1000.0 * nd_dist.max_time(elapsed, device=dev) / args.steps, 3),
+                      "ms_per_step_median": round(statistics.median(step_ms), 3)} if args.full else None)
             g = torch.cuda.CUDAGraph()
             state["outs"] = None
             with torch.cuda.graph(g):
@@ -443,14 +487,20 @@ def bench_decode(args, rank, world, local, dev, bg, Z, T, B, cus=256, ceilings=N
                 state["outs"] = g_outs
 
             elapsed, _, step_ms = timed(args, local, dev, gstep, Prof(False, 0))
-            graph_info = {"replay": True, "eager": eager}
+            graph_info = {"replay": True, "eager": eager} if args.full else {"replay": True}
         counts = ber_counts(state["outs"])  # BER / FER per iteration, decoder convention bit = LLR > 0
-        # the reference helper itself on the same outputs (literal rule bit = LLR < 0: ~1 - BER)
-        from boosted_neural_ldpc_decoder.Functions import Functions
-        (lit_bits, _), (lit_frames, _) = Functions.evaluate_ber_fer(
-            torch.zeros((B, N * Z), dtype=torch.uint8, device=dev), state["outs"])
-        n_cpu = min(B, 2048)  # the codewords the CPU baseline may decode: their GPU outputs, kept for comparison
-        gpu_last = state["outs"][-1][:n_cpu].cpu()
+        if args.full:
+            # the reference helper itself on the same outputs (literal rule bit = LLR < 0: ~1 - BER)
+            from boosted_neural_ldpc_decoder.Functions import Functions
+            (lit_bits, _), (lit_frames, _) = Functions.evaluate_ber_fer(
+                torch.zeros((B, N * Z), dtype=torch.uint8, device=dev), state["outs"])
+        if world == 1 and not args.no_cpu_baseline and not ucn:
+            n_cpu = min(B, 2048)  # the codewords the CPU baseline may decode: their GPU outputs, kept for comparison
+            gpu_last = state["outs"][-1][:n_cpu].cpu()
+        if args.dump_outputs:  # the list of T posteriors the module call returned in the last timed step
+            rows = torch.as_tensor(dump_rows(B, 4 * T * N * Z), device=dev)
+            dump_outputs(args.dump_outputs, rank, world,
+                         {f"posterior_iter{t:02d}": o.index_select(0, rows) for t, o in enumerate(state["outs"])})
         state.clear()
         # count-only decode: the same decode with the counting fused into the kernel and
         # no posteriors written -- reported beside the headline, never as `value`
@@ -527,8 +577,9 @@ def bench_decode(args, rank, world, local, dev, bg, Z, T, B, cus=256, ceilings=N
         res["ber_sweep"] = sweep
     # D7: Functions.evaluate_ber_fer's literal value on the same outputs (rank 0's shard; its inverted
     # decision rule reports ~1 - BER)
-    res["ber"]["evaluate_ber_fer_literal_rank0"] = {"bit_errors_last_iter": lit_bits[-1], "bits": B * N * Z,
-                                                    "frame_errors_last_iter": lit_frames[-1], "frames": B}
+    if lit_bits is not None:
+        res["ber"]["evaluate_ber_fer_literal_rank0"] = {"bit_errors_last_iter": lit_bits[-1], "bits": B * N * Z,
+                                                        "frame_errors_last_iter": lit_frames[-1], "frames": B}
     if prof is not None:
         res["roofline"] = roofline(prof, kernel_bytes(B, E, N, Z, T), args.steps, B, Z, world, tag,
                                    4 * (2 * T * E * Z + (T + 1) * N * Z), ceilings, pmc_workload(args) + f"_B{B}",
@@ -574,9 +625,19 @@ def bench_train(args, rank, world, local, dev, bg, Z, T, B, cus=256, ceilings=No
         model._apply_constraints()
         state["loss"] = loss.detach()
         state["last"] = outs[-1].detach()
+        state["n"] = state.get("n", 0) + 1
+        if args.dump_outputs and state["n"] == args.warmup + args.steps:  # the last timed step: keep all T posteriors
+            state["outs"] = outs
 
     elapsed, prof, step_ms = timed(args, local, dev, step, Prof(not args.no_profile, args.steps * (6 * T + 8)))
     counts = ber_counts([state["last"]])
+    if args.dump_outputs:  # the last timed step's loss and posteriors, and the parameters it left
+        rows = torch.as_tensor(dump_rows(B, 4 * T * N * Z), device=dev)
+        arrays = {f"posterior_iter{t:02d}": o.index_select(0, rows) for t, o in enumerate(state["outs"])}
+        arrays["loss"] = state["loss"].reshape(1)
+        arrays.update({f"param_{n}": p for n, p in model.named_parameters()})
+        dump_outputs(args.dump_outputs, rank, world, arrays)
+    state["outs"] = None
     elapsed = nd_dist.max_time(elapsed, device=dev)
     med = nd_dist.max_time(statistics.median(step_ms) / 1000.0, device=dev)
     counts = nd_dist.sum_counts(counts).cpu().numpy()

@@ -21,8 +21,18 @@ the torch of the machine they run on); idx[(KMAX >> SH) + 2] (bucket b = key >> 
 entries[n_entries] = key | dir << 31, ascending in key (key = |x| bits; dir 1: torch.tanh is one ulp
 above the correctly rounded value, 0: one ulp below); overrides[n_override] = (key, result bits).
 
-Usage: python3 gen_tanh_table.py OUT.bin
+The table the fixtures under tests/golden/ were made with is committed in packed form
+(tests/golden/nldpc_tanh_ref.xz, a quarter of a megabyte) and the build unpacks it, byte for byte, into
+lib/nldpc_tanh_ref.bin: torch.tanh differs between hosts (see above), so a table measured on the build
+host would not reproduce the fixtures everywhere.  Packed layout: xz of the 88 header bytes, the
+overrides, the four byte planes (low byte first) of the entries' key differences, and the dir bits
+(numpy.packbits); idx is recomputed from the keys.
+
+Usage: python3 gen_tanh_table.py OUT.bin               measure this host's torch.tanh
+       python3 gen_tanh_table.py --pack IN.bin OUT.xz
+       python3 gen_tanh_table.py --unpack IN.xz OUT.bin
 """
+import lzma
 import os
 import struct
 import sys
@@ -86,5 +96,62 @@ def main(out):
     print(f"gen_tanh_table: {len(ent)} corrections, {len(overrides)} overrides -> {out}")
 
 
+def _index(keys, sh, kmax):
+    nb = (kmax >> sh) + 2
+    idx = np.searchsorted(keys, (np.arange(nb, dtype=np.uint64) << np.uint64(sh)).astype(np.uint32)).astype(np.uint32)
+    idx[-1] = len(keys)
+    return idx
+
+
+def pack(src, out):
+    raw = np.fromfile(src, dtype=np.uint32)
+    magic, ver, sh, kmax, n, nov = (int(v) for v in raw[:6])
+    if magic != 0x4841544E or ver != 2:
+        raise SystemExit(f"gen_tanh_table: {src} is not a version 2 table")
+    nb = (kmax >> sh) + 2
+    ent, ov = raw[22 + nb:22 + nb + n], raw[22 + nb + n:]
+    keys = ent & np.uint32(0x7FFFFFFF)
+    if len(ov) != 2 * nov or not np.array_equal(raw[22:22 + nb], _index(keys, sh, kmax)):
+        raise SystemExit(f"gen_tanh_table: {src} is inconsistent")
+    delta = np.diff(keys, prepend=np.uint32(0))
+    planes = b"".join(((delta >> np.uint32(8 * i)) & np.uint32(0xFF)).astype(np.uint8).tobytes() for i in range(4))
+    blob = raw[:22].tobytes() + ov.tobytes() + planes + np.packbits((ent >> np.uint32(31)).astype(np.uint8)).tobytes()
+    with open(out, "wb") as f:
+        f.write(lzma.compress(blob, preset=9 | lzma.PRESET_EXTREME))
+    unpack(out, out + ".check")
+    same = open(out + ".check", "rb").read() == raw.tobytes()
+    os.remove(out + ".check")
+    if not same:
+        raise SystemExit("gen_tanh_table: the packed table does not unpack to its source")
+    print(f"gen_tanh_table: {src} ({raw.nbytes} bytes) -> {out} ({os.path.getsize(out)} bytes)")
+
+
+def unpack(src, out):
+    with open(src, "rb") as f:
+        blob = lzma.decompress(f.read())
+    hdr = np.frombuffer(blob[:88], dtype=np.uint32)
+    magic, ver, sh, kmax, n, nov = (int(v) for v in hdr[:6])
+    if magic != 0x4841544E or ver != 2 or len(blob) != 88 + 8 * nov + 4 * n + (n + 7) // 8:
+        raise SystemExit(f"gen_tanh_table: {src} is not a packed version 2 table")
+    o = 88 + 8 * nov
+    delta = np.zeros(n, dtype=np.uint32)
+    for i in range(4):
+        delta |= np.frombuffer(blob[o + i * n:o + (i + 1) * n], dtype=np.uint8).astype(np.uint32) << np.uint32(8 * i)
+    keys = np.cumsum(delta, dtype=np.uint64).astype(np.uint32)
+    dirs = np.unpackbits(np.frombuffer(blob[o + 4 * n:], dtype=np.uint8))[:n].astype(np.uint32)
+    tmp = out + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(blob[:88])
+        f.write(_index(keys, sh, kmax).tobytes())
+        f.write((keys | dirs << np.uint32(31)).tobytes())
+        f.write(blob[88:o])
+    os.replace(tmp, out)
+
+
 if __name__ == "__main__":
-    main(sys.argv[1])
+    if sys.argv[1] == "--pack":
+        pack(sys.argv[2], sys.argv[3])
+    elif sys.argv[1] == "--unpack":
+        unpack(sys.argv[2], sys.argv[3])
+    else:
+        main(sys.argv[1])

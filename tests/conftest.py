@@ -19,7 +19,8 @@ def pytest_configure(config):
 
 # GPU tests that start rank processes go first: they must be started by a process that has not touched
 # the GPU yet (test_distributed.py), whatever order the other test files would run in
-_FIRST = ("test_bench_launches_ranks_and_sums_counts", "test_two_rank_sharded_decode_on_gpu")
+_FIRST = ("test_bench_launches_ranks_and_sums_counts", "test_bench_plain_run_dumps_the_last_steps_outputs",
+          "test_two_rank_sharded_decode_on_gpu")
 
 
 def pytest_collection_modifyitems(config, items):

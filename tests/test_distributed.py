@@ -178,6 +178,57 @@ def test_bench_launches_ranks_and_sums_counts():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_dumps_the_last_steps_outputs(tmp_path):
+    """A plain bench.py run (no --full) as a child process: --steps sets the timed steps, the line carries
+    ms_per_step and none of what --full measures beside the headline, and --dump-outputs writes the T
+    posteriors of the last timed step as float32 .npy (every codeword of a batch this small).  They equal,
+    bit for bit, the CPU oracle's decode of the same Philox codewords (oracle/philox.py); the parent never
+    touches the GPU."""
+    import json
+    import subprocess
+    from nldpc.channel import sigma_for
+    from oracle.ldpc_oracle import OracleGraph, neural_forward
+    from oracle.philox import awgn_llr
+    B, T, Z = 5, 3, 384
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--batch", str(B), "--iters", str(T), "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, f"bench.py exited {r.returncode}:\n{r.stdout[-2000:]}\n{r.stderr[-3000:]}"
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    # value = B / (time of one step); ms_per_step is rounded to 1e-3 ms and value to 0.1
+    assert line["value"] == pytest.approx(B * 1000.0 / line["ms_per_step"], rel=1e-3 + 5e-4 / line["ms_per_step"])
+    assert line["unit"] == "codewords/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    for k in ("side_lines", "roofline", "cpu_baseline", "count_only", "ber_sweep"):
+        assert k not in line, f"a plain run reports {k}"
+    bg = np.loadtxt(os.path.join(ROOT, "resources", "basegraph2_set0.txt"), int, delimiter="\t")
+    M, N = bg.shape
+    g = OracleGraph(bg, Z)
+    x = torch.from_numpy(awgn_llr(B, N * Z, sigma_for(2.0, (N - M) / (N - 2)), seed=2042)).reshape(B, N, Z)
+    with torch.no_grad():
+        ref = neural_forward(g, x, [torch.full((g.E,), 0.5) for _ in range(T)], [torch.zeros(g.E) for _ in range(T)])
+    assert sorted(os.listdir(out)) == [f"posterior_iter{t:02d}.npy" for t in range(T)]
+    for t in range(T):
+        o = np.load(out / f"posterior_iter{t:02d}.npy")
+        assert o.dtype == np.float32 and o.shape == (B, N * Z)
+        assert np.array_equal(o, ref[t].numpy().reshape(B, N * Z)), f"iteration {t}: dump differs from the oracle"
+    assert line["ber"]["bit_errors_last_iter"] == int((ref[-1] > 0).sum())
+
+
+def test_bench_dump_rows_are_a_fixed_bounded_sample():
+    """--dump-outputs keeps every codeword of a small batch and, of a large one, the first, the last and a
+    seeded choice of the others that stays within the byte bound and is the same on every call."""
+    import bench
+    row = 4 * 20 * 52 * 384  # one cfg3 codeword's T posteriors
+    assert np.array_equal(bench.dump_rows(7, row), np.arange(7))
+    rows = bench.dump_rows(65536, row)
+    assert rows[0] == 0 and rows[-1] == 65535 and np.all(np.diff(rows) > 0)
+    assert 2 <= len(rows) and len(rows) * row <= bench.DUMP_BYTES <= 64 << 20
+    assert np.array_equal(rows, bench.dump_rows(65536, row))
+
+
+@pytest.mark.gpu
 def test_two_rank_sharded_decode_on_gpu():
     """Two rank processes decode the two shards of a BG2 z=384 batch with the product (HIP kernels,
     on-device channel at the rank's b_offset) and all-reduce the counters: the result equals one

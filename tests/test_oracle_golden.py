@@ -184,3 +184,29 @@ def test_tanh_table_reproduces_torch_tanh():
     x = torch.cat([x, -x])
     got = lo._tanh(x)
     assert torch.equal(got, torch.tanh(x)), f"{(got != torch.tanh(x)).sum().item()} values differ"
+
+
+def test_committed_tanh_table_packs_and_unpacks(tmp_path):
+    """tests/golden/nldpc_tanh_ref.xz (the table the fixtures were made with; the build unpacks it into lib/)
+    unpacks to a version 2 table with ascending keys and a consistent bucket index, and packing that
+    table again unpacks to the same bytes (gen_tanh_table.py --pack / --unpack)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(
+        "gen_tanh_table", os.path.join(ROOT, "neural-ldpc-decoder-torch_amd", "csrc", "gen_tanh_table.py"))
+    gt = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gt)
+    a, b = str(tmp_path / "a.bin"), str(tmp_path / "b.bin")
+    gt.unpack(os.path.join(GOLDEN, "nldpc_tanh_ref.xz"), a)
+    raw = np.fromfile(a, dtype=np.uint32)
+    magic, ver, sh, kmax, n, nov = (int(v) for v in raw[:6])
+    nb = (kmax >> sh) + 2
+    assert (magic, ver) == (0x4841544E, 2) and len(raw) == 22 + nb + n + 2 * nov
+    keys = raw[22 + nb:22 + nb + n] & np.uint32(0x7FFFFFFF)
+    assert np.all(np.diff(keys.astype(np.int64)) > 0) and int(keys[-1]) <= kmax
+    assert np.array_equal(raw[22:22 + nb], gt._index(keys, sh, kmax))
+    gt.pack(a, str(tmp_path / "a.xz"))  # (checks the round trip itself, too)
+    gt.unpack(str(tmp_path / "a.xz"), b)
+    assert open(a, "rb").read() == open(b, "rb").read()
+    built = os.path.join(ROOT, "neural-ldpc-decoder-torch_amd", "lib", "nldpc_tanh_ref.bin")
+    if os.path.exists(built) and not os.environ.get("NLDPC_TANH_TABLE"):
+        assert open(built, "rb").read() == open(a, "rb").read(), "lib/nldpc_tanh_ref.bin is not the committed table"

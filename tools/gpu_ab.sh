@@ -13,7 +13,7 @@ for v in ${VARIANTS}; do
     if [ -z "${NOCHECK}" ]; then
         NLDPC_LIB_PATH=$L timeout -k 10 180 python -u tools/ab_check.py ${CHECK_KINDS} > $O/abchk_$n.log 2>&1 || { echo "$v check failed rc=$?"; tail -5 $O/abchk_$n.log; exit 1; }
     fi
-    NLDPC_LIB_PATH=$L timeout -k 10 240 python -u bench.py --steps ${STEPS:-6} --warmup 2 \
+    NLDPC_LIB_PATH=$L timeout -k 10 240 python -u bench.py --full --steps ${STEPS:-6} --warmup 2 \
         --no-cpu-baseline --no-sweep --no-count-only --no-side-lines ${BENCH_ARGS} > $O/ab_$n.log 2>&1 || { echo "$v failed rc=$?"; tail -5 $O/ab_$n.log; exit 1; }
     python3 - $v $O/ab_$n.log $O/abchk_$n.log <<'PY'
 import json, os, sys

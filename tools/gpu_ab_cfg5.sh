@@ -9,7 +9,7 @@ for rnd in $(seq 1 ${ROUNDS:-2}); do
 for v in ${VARIANTS}; do
     n=${v//\//_}
     NLDPC_LIB_PATH=$R/neural-ldpc-decoder-torch_amd/$v/libnldpc.so timeout -k 10 300 python -u bench.py --workload cfg5 \
-        --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline ${BENCH_ARGS} > $O/ab_${n}_$rnd.log 2>&1 || { echo "$v failed rc=$?"; tail -5 $O/ab_${n}_$rnd.log; exit 1; }
+        --full --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline ${BENCH_ARGS} > $O/ab_${n}_$rnd.log 2>&1 || { echo "$v failed rc=$?"; tail -5 $O/ab_${n}_$rnd.log; exit 1; }
     python3 - $v $O/ab_${n}_$rnd.log <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][-1])

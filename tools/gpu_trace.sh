@@ -4,5 +4,5 @@ set -o pipefail
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${TAG:-trace}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- \
-    python3 $R/bench.py --no-cpu-baseline ${BENCH_ARGS} > $O/bench.log 2>&1
+    python3 $R/bench.py --full --no-cpu-baseline ${BENCH_ARGS} > $O/bench.log 2>&1
 rc=$?; grep '^{' $O/bench.log | tail -1 | cut -c1-300; echo "exit $rc"; exit $rc

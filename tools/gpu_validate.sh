@@ -11,10 +11,10 @@ if [ -z "$NOTESTS" ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { echo "smoke failed"; tail -5 $O/smoke.log; exit 1; }
   tail -1 $O/smoke.log
 fi
-timeout -k 10 600 python bench.py > $O/bench.log 2>&1 || { echo "bench failed"; tail -5 $O/bench.log; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench.log 2>&1 || { echo "bench failed"; tail -5 $O/bench.log; exit 1; }
 if [ -z "$NOUCN" ]; then
-  timeout -k 10 300 python bench.py --workload cfg3ucn --kind MS --no-cpu-baseline --no-sweep > $O/bench_ucn_ms.log 2>&1 &&
-  timeout -k 10 300 python bench.py --workload cfg3ucn --kind QMS --no-cpu-baseline --no-sweep > $O/bench_ucn_qms.log 2>&1 || { echo "ucn bench failed"; exit 1; }
+  timeout -k 10 300 python bench.py --full --workload cfg3ucn --kind MS --no-cpu-baseline --no-sweep > $O/bench_ucn_ms.log 2>&1 &&
+  timeout -k 10 300 python bench.py --full --workload cfg3ucn --kind QMS --no-cpu-baseline --no-sweep > $O/bench_ucn_qms.log 2>&1 || { echo "ucn bench failed"; exit 1; }
 fi
 python3 - $O <<'PY'
 import json, os, sys
@@ -30,6 +30,6 @@ for f in ("bench", "bench_ucn_ms", "bench_ucn_qms"):
 PY
 if [ -z "$NOTRACE" ]; then
   cd /tmp && export TMPDIR=/tmp &&
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_prof.log 2>&1 || { echo "trace failed"; exit 1; }
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_prof.log 2>&1 || { echo "trace failed"; exit 1; }
 fi
 echo "validate done"
