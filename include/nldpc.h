@@ -124,7 +124,8 @@ int nldpc_graph_kernels(const nldpc_graph* g, uint32_t* mask);
 int nldpc_fast_path(const nldpc_graph* g, const nldpc_cfg* cfg, int64_t B, int32_t T, int32_t saving,
                     int32_t* eligible);
 /*      (ABI 3) saving = 2 / 3 asks the same for nldpc_forward_count (all-zero codeword, decoder convention /
- *      any convention or codeword), whose fused kernels are separate variants. */
+ *      any convention or codeword), whose fused kernels are separate variants; saving = 4 asks it for
+ *      nldpc_forward_early_stop (additionally: no UCN, first_iter == 0). */
 
 /* ---- decode forward: replaces NeuralLDPCDecoder.forward (NeuralLDPCDecoder.py:44-100) and
  *      BoostedNeuralLDPCDecoder.forward (BoostedNeuralLDPCDecoder.py:260-538).
@@ -193,6 +194,32 @@ int nldpc_ber_count(const float* llr, const uint8_t* y, int64_t B, int64_t L, in
 int nldpc_forward_count(const nldpc_graph* g, const nldpc_cfg* cfg, int64_t B, int32_t T, const float* xa,
                         const float* w_cn, const float* w_ucn, const float* bias, const float* w_vn,
                         const uint8_t* y, int32_t convention, int64_t* counts, void* stream);
+
+/* ---- parity-check syndrome weight (additive to ABI 4): is a decoder output a codeword?
+ *   llr [B][N*Z]; unsat int32 [B] device, overwritten: the number of the M*Z lifted check rows whose XOR of the
+ *   hard decisions over the row's edges is 1 (edge (i, j, s) joins check copy h to variable copy (h + s) mod Z,
+ *   as nldpc_graph_edges lists them); 0 = the hard decision is a codeword.  convention as nldpc_ber_count
+ *   (0: bit = LLR > 0, an exact 0 is bit 0).  Reads the graph's device edge tables; any graph and Z, no fused
+ *   kernel needed; stream-ordered, no synchronisation, no allocation. */
+int nldpc_syndrome(const nldpc_graph* g, const float* llr, int64_t B, int32_t convention, int32_t* unsat,
+                   void* stream);
+
+/* ---- early-stopping decode (additive to ABI 4): nldpc_forward, stopped per codeword at the first iteration whose
+ *      hard decision (LLR > 0) satisfies every parity check.  With t*(b) the smallest t in 0..T-1 whose posterior
+ *      has syndrome weight 0, or T-1 if there is none:
+ *   out    [B][N*Z]  out[b] = the posterior of iteration t*(b), bit for bit what nldpc_forward writes there
+ *   iters  int32 [B] t*(b) + 1, or NULL
+ *   unsat  int32 [B] syndrome weight of out[b] (0 = a codeword), or NULL; filled by an nldpc_syndrome launch on out
+ *   other arguments as nldpc_forward_count.  Inference only: no saved buffer, c2v_in == 0, first_iter == 0, no UCN.
+ *   Runs the register-resident early-stop kernels (a MODE of their own; the parity of every check copy is taken
+ *   inside the kernel each iteration, and a workgroup leaves as soon as all its codewords have stopped), which the
+ *   library builds for its compiled base graphs only: a run-time compiled geometry (nldpc_graph_attach_kernel) has
+ *   no such kernel and gets NLDPC_EUNSUPPORTED like every other ineligible call (c2v_in, first_iter > 0, T > 64,
+ *   UCN, NLDPC_FLAG_STREAM, no compiled graph); nldpc_fast_path with saving = 4 answers for this entry point.
+ *   The fallback is nldpc_forward with all T outputs, nldpc_syndrome on each and a selection (nldpc.decode does it). */
+int nldpc_forward_early_stop(const nldpc_graph* g, const nldpc_cfg* cfg, int64_t B, int32_t T, const float* xa,
+                             const float* w_cn, const float* w_ucn, const float* bias, const float* w_vn,
+                             float* out, int32_t* iters, int32_t* unsat, void* stream);
 
 /* ---- multi-iteration BCE loss (config 5's training loss): replaces LDPCDecoderLoss.forward with
  *      LossType.BCE over a list of outputs and one label tensor

@@ -315,8 +315,11 @@ class Spec:
         self.hb_cols = cols  # column of each C-order edge
 
 
-def emit(S: Spec) -> str:
+def emit(S: Spec, estop: bool = False) -> str:
+    """estop: the early-stopping decode (MODE 7, a unit of its own).  The text of every other MODE is emitted with
+    estop False and does not change: every line the early stop adds is behind `if estop`."""
     Z, G, Q, ZT, NZ = S.Z, S.G, S.Q, S.ZT, S.N * S.Z
+    assert not estop or (S.pipe and G <= 32)  # (the stopped codewords are a 32-bit mask)
     L = []
     w = L.append
     CF = S.chunk_floats
@@ -345,6 +348,18 @@ def emit(S: Spec) -> str:
     w("// check-row LDS addresses from one 32-bit base (ROADDR); in the QMS / SP kernels it measured slower")
     w("#define ROA (KIND == NLDPC_NEURAL || KIND == NLDPC_MS)")
     assert NZ < 65536  # per-codeword error counts are packed two to an LDS word
+
+    if estop:
+        # MODE 7: MODE 0 with a parity check of every posterior.  The hard decisions (LLR > 0) of the
+        # posterior of iteration it-1 go through the UCN bit array (register columns, vn_p of iteration it) and cdm
+        # (degree-1 columns, the check-node threads of iteration it-1).  After iteration it's first barrier every
+        # thread takes the parity of its check copies (par_p, the UCN gather) and the odd ones are counted per
+        # codeword in LDS (cnt_all[g * 32 + (it & 1)]).  At that point the output buffer (a.outs.p[t] are all the
+        # same pointer) holds exactly out_{it-1}: its register columns were stored by this iteration's vn_p, its
+        # degree-1 columns by the check nodes of it-1.  After one more barrier every wave reads the counts: a
+        # codeword with none is frozen (its lanes' offsets leave every descriptor's range, so every later store of
+        # its posterior is dropped), and the workgroup leaves the loop when all its live codewords are frozen.
+        w("// early stop (MODE 7): no UCN (the host checks); int32 iteration counts [B] through a.cnt")
 
     # Register state of part p: one float array per lane copy q (cs{q}[slot]).  The channel values a thread
     # needs every iteration are loaded once into registers (xs{q} for its register columns; those of the
@@ -499,6 +514,8 @@ def emit(S: Spec) -> str:
                     if not final:
                         app0 = f"(a.first_iter > 0 ? bload(apr, vo, {X(j, q)}) : chan<KIND>(xs{q}[{n}], a))"
                         w(f"            if (ucn_) app_or(appw, {j * S.WZX}, u + {q * ZT}, (it == 0 ? {app0} : y_) >= 0.f);")
+                        if estop:  # y_ is the posterior of iteration it-1; its bit is LLR > 0
+                            w(f"            if (it >= 1) app_or(appw, {j * S.WZX}, u + {q * ZT}, y_ > 0.f);")
                     w("            }")
                 w("        }")
                 w("        __builtin_amdgcn_sched_barrier(0);")
@@ -713,6 +730,8 @@ def emit(S: Spec) -> str:
                         w(f"                else y_ = posterior<KIND>(xo_, {pm}, a);")
                         w(f"                if (UCN_ON) {bit_set('cdm', ix, 'y_ >= 0.f')};")
                         w("            }")
+                        if estop:  # this posterior's hard decision (LLR > 0) for the next iteration's parity check
+                            w(f"            {bit_set('cdm', ix, 'y_ > 0.f')};")
                         if "d1post" in SKIP:  # (timing experiment: no degree-1 posterior stores)
                             w("            asm volatile(\"\" :: \"v\"(y_));")
                         else:
@@ -734,6 +753,35 @@ def emit(S: Spec) -> str:
                     rc_load(n + 1)
                 w("    __builtin_amdgcn_sched_barrier(0);")
                 rc_compute(n)
+            w("}")
+
+    # ---------------------------------------------------------------- early stop: parity of a part's check copies
+    # (the UCN gather: the bit word of each edge's variable copy, shifted to the copy's bit and XOR-ed over the row;
+    # a degree-1 edge's bit is the check-node thread's own, cdm) -- the number of this thread's odd check copies
+    if estop:
+        for p in range(S.P):
+            w(f"__device__ __forceinline__ int par_p{p}(int u, const uint32_t* appw, const uint32_t (&cdm)[{nwords(p)}]) {{")
+            w("    asm volatile(\"\" : \"+v\"(u));")
+            w("    int n_ = 0;")
+            for ci in range(len(S.chunks)):
+                for i, q in S.cn_units[ci][p]:
+                    es = S.row_edges[i]
+                    ks = [(k, e) for k, e in enumerate(es) if e not in d1set]
+                    w(f"    {{  // row {i} copy {q}")
+                    w("        uint32_t par_ = 0;")
+                    for k, e in ks:
+                        c, dvu = rot(e, q)
+                        j = int(S.hb_cols[e])
+                        vexpr = f"(uint32_t)u + {c}u" if c + ZT <= Z else f"min((uint32_t)u + {c}u, (uint32_t)u + {c - Z}u)"
+                        w(f"        const uint32_t v{k}_ = {vexpr}; const uint32_t w{k}_ = appw[{j * S.WZX} + (v{k}_ >> 5)];")
+                    for k, e in ks:
+                        w(f"        par_ ^= w{k}_ >> (v{k}_ & 31u);")
+                    for k, e in enumerate(es):
+                        if e in d1set:
+                            w(f"        par_ ^= {bit_get('cdm', S.cd_index[p].index((e, q)))};")
+                    w("        n_ += (int)(par_ & 1u);")
+                    w("    }")
+            w("    return n_;")
             w("}")
 
     # ---------------------------------------------------------------- the kernel
@@ -769,7 +817,7 @@ def emit(S: Spec) -> str:
         w("template <int KIND, int MODE>")
         w(f"__device__ __forceinline__ void run_p{p}(const FusedArgs& a, float* lds, int u, int64_t blk, int nlive, "
           f"rsrc_t xr, uint32_t vo, rsrc_t cr, uint32_t vc, uint32_t vm, int* cntl, uint32_t* app_all, uint32_t* appw, bool dup_, "
-          f"const float* lds_all{', int ub' if S.uremat else ''}) {{")
+          f"const float* lds_all{', int ub' if S.uremat else ''}{', int* es_cnt, int g' if estop else ''}) {{")
         # UREMAT (the SAVE kernels of a one-codeword, unpadded geometry): the lane offsets u / vo / vc / vm are
         # re-derived from the wave-uniform base ub and the lane id before each phase, so none of them lives across
         # the iteration (the QMS training forward at the 128-VGPR cap spilled them and reloaded each phase with a
@@ -834,6 +882,11 @@ def emit(S: Spec) -> str:
         w(f"        for (int i_ = threadIdx.x; i_ < {S.G_lds * S.N * S.WZX}; i_ += {S.threads}) app_all[i_] = 0u;")
         w("        __syncthreads();")
         w("    }")
+        if estop:
+            w("    uint32_t es_stop = 0;  // frozen codewords of the workgroup (wave-uniform, the same in every wave)")
+            w("    const uint32_t es_live = nlive >= 32 ? ~0u : (1u << nlive) - 1u;")
+            w(f"    for (int i_ = threadIdx.x; i_ < {S.G_lds * S.N * S.WZX}; i_ += {S.threads}) app_all[i_] = 0u;")
+            w("    __syncthreads();")
         w("    for (int it = 0; it < a.T; ++it) {")
         stamp(0)
         w("        if (KIND != NLDPC_NEURAL && WVN_ON) {")
@@ -967,6 +1020,34 @@ def emit(S: Spec) -> str:
                 if k < len(phases) - 1:
                     # (timing experiment SKIP=sync: no barrier -- racy results, the cost of waiting at them)
                     w("        __builtin_amdgcn_sched_barrier(0);" if "sync" in SKIP else "        __syncthreads();")
+                if estop and k == 0:
+                    # The parity check of the posterior of it-1 and the exit decision (the bits of this iteration's vn_p
+                    # are visible: the barrier above).  `it` is wave-uniform, so every wave takes the same branch and
+                    # meets the same barriers.  Every wave reads the same LDS words after the barrier below: the counts
+                    # in cnt_all[.][it & 1], complete (the adds precede that barrier) and written by nobody again before
+                    # the same barrier of iteration it+1 (that iteration adds to the other word, which is cleared here,
+                    # after its last readers -- the decision of iteration it-1 -- passed the barrier above).  So es_stop
+                    # is the same in every wave, all waves leave the loop at this point of the same iteration, and no
+                    # barrier follows the loop.
+                    w("        if (it >= 1) {")
+                    w(f"            const int esn = par_p{p}(u, appw, cdm);")
+                    w("            if (!dup_ && esn) atomicAdd(es_cnt + g * 32 + (it & 1), esn);  // (lanes repeating a live one add nothing)")
+                    w("            __syncthreads();")
+                    w("            uint32_t z_ = 0;")
+                    w("#pragma unroll")
+                    w(f"            for (int g_ = 0; g_ < {G}; ++g_) z_ |= (es_cnt[g_ * 32 + (it & 1)] == 0 ? 1u : 0u) << g_;")
+                    w("            z_ = (uint32_t)__builtin_amdgcn_readfirstlane((int)z_) & es_live & ~es_stop;  // codewords that stop at t* = it-1")
+                    w("            if ((z_ >> g) & 1u) {")
+                    if p == list(PARTS or range(S.P))[0]:
+                        w("                if (u == 0 && !dup_ && a.cnt) reinterpret_cast<int32_t*>(a.cnt)[blk + g] = it;  // t* + 1")
+                    w("                vo = 0x80000000u;  // frozen: every later store of this codeword's posterior is dropped")
+                    w("            }")
+                    w("            es_stop |= z_;")
+                    w("            if (es_stop == es_live) break;")
+                    # (every check copy has read the bits: cleared for the next iteration's vn_p, several barriers away)
+                    w(f"            for (int i_ = threadIdx.x; i_ < {S.G_lds * S.N * S.WZX}; i_ += {S.threads}) app_all[i_] = 0u;")
+                    w(f"            if (threadIdx.x < {G}) es_cnt[threadIdx.x * 32 + ((it + 1) & 1)] = 0;")
+                    w("        }")
             # a K-odd schedule ends with [R_{K-1}] alone after [R_{K-2}... ]: the next W0 (buffer 0) follows
             # R_{K-1} (buffer 0) in other waves -> keep a barrier; K even: R_{K-1} reads buffer 1
             if K % 2 == 1:
@@ -982,6 +1063,9 @@ def emit(S: Spec) -> str:
             w(remat)
         w(f"    post_p{p}<KIND, MODE>({state_args(p)}, {x_args(p)}, a, vo, a.T, lr, vm, xr, lm, ps, appw, u, apr);")
         w(f"    if constexpr (CNT) {{ if (dup_) ps.ec = 0; ps.{cnt_flush}({cnt_slot}, a.T - 1); }}")
+        if estop:  # codewords that never stopped: t* = T-1 (the frozen ones' stores are dropped)
+            if p == list(PARTS or range(S.P))[0]:
+                w("    if (u == 0 && !dup_ && g < nlive && !((es_stop >> g) & 1u) && a.cnt) reinterpret_cast<int32_t*>(a.cnt)[blk + g] = a.T;")
         w("    if (a.c2v_out) {")
         for q in range(Q):
             for k, e in enumerate(S.slots[p]):
@@ -1018,10 +1102,12 @@ def emit(S: Spec) -> str:
     w(f"    __shared__ uint32_t app_all[{S.G_lds * S.N * S.WZX}];  // UCN: bit (j, v) = APP[j][v] >= 0, per codeword")
     w(f"    uint32_t* appw = app_all + (dup_ ? {G} : g) * {S.N * S.WZX};")
     w(f"    if constexpr (CNT) {{ for (int i = t; i < {G * 32}; i += {S.threads}) cnt_all[i] = 0; }}  // first use after iteration 0's barriers")
+    if estop:
+        w(f"    for (int i = t; i < {G * 32}; i += {S.threads}) cnt_all[i] = 0;  // early stop: parity counts, first added to in iteration 1")
     if S.uremat:
         w("    const int ub = __builtin_amdgcn_readfirstlane(u - lane_id());  // (UREMAT) u of the wave's lane 0")
     each_part("run_p{p}<KIND, MODE>(a, lds, u, blk, nlive, xr, vo, cr, vc, vm, cnt_all + g * 32, app_all, appw, dup_, lds_all"
-              + (", ub)" if S.uremat else ")"), indent="    ")
+              + (", ub" if S.uremat else "") + (", cnt_all, g)" if estop else ")"), indent="    ")
     w("    if constexpr (CNT) {")
     w("        __syncthreads();")
     w("        if (t < a.T) count_iteration(a, cnt_all, nlive, t);")
@@ -1517,6 +1603,7 @@ BWD_STAGE = {0: 0, 1: 0, 2: 1, 3: 4}
 BWD_NS = {0: "fusedbs", 1: "fusedbs", 2: "fusedbq", 3: "fusedb"}
 
 MODES = (0, 1, 2, 3)  # forward kernels: decode / decode + save for backward / count-only (all-zero, LLR > 0) / count-only (general)
+# (and, in units of their own: MODE 6 the specialised UCN decode, _s0u; MODE 7 the early-stopping decode, _s7)
 
 
 def jit_source(hb, Z, kind, mode):
@@ -1557,6 +1644,7 @@ def main():
         return
     if sys.argv[1] == "--list":  # file names, for the Makefile
         print(" ".join([f"fused_{t[0]}_s{v}.hip" for t in SPECS for v in MODES] + [f"fused_{t[0]}_s0u.hip" for t in SPECS] +
+                       [f"fused_{t[0]}_s7.hip" for t in SPECS] +
                        [f"fused_{t[0]}_bwd.hip" for t in SPECS] + ["fused_table.hip"]))
         return
     outdir, res = sys.argv[1], sys.argv[2]
@@ -1624,6 +1712,19 @@ def main():
         src.append("}")
         src.append("}  // namespace nldpc")
         write(f"fused_{S.tag}_s0u.hip", src)
+        # the early-stopping decode, MODE 7, every kind: a unit of its own with its own emitted text (emit(estop=True)), so
+        # the other units' sources do not change
+        src = list(head)
+        src.append(emit(S, estop=True) if on else "")
+        src.append(f"uint32_t fused_{S.tag}_sig_s7() {{ return kFusedArgsSig; }}  // this unit's FusedArgs layout")
+        src.append(f"void* fused_{S.tag}_kernel_s7(int kind) {{")
+        if on:
+            for k in kinds:
+                src.append(f"    if (kind == {k}) return reinterpret_cast<void*>(&fused_{S.tag}::kernel<{k}, 7>);")
+        src.append("    return nullptr;")
+        src.append("}")
+        src.append("}  // namespace nldpc")
+        write(f"fused_{S.tag}_s7.hip", src)
         # backward kernels: the fp32-message kinds and QMS (int8 codes) stage their saved messages in LDS
         # beside chunk images sized for them, so they are two generated namespaces
         src = list(head)
@@ -1658,6 +1759,8 @@ def main():
         src.append(f"void* fused_{S.tag}_bwd_tied(int kind);")
         src.append(f"void* fused_{S.tag}_kernel_s1t(int kind);")
         src.append(f"void* fused_{S.tag}_kernel_s0u(int kind);")
+        src.append(f"void* fused_{S.tag}_kernel_s7(int kind);")
+        src.append(f"uint32_t fused_{S.tag}_sig_s7();")
         for v in MODES:
             src.append(f"uint32_t fused_{S.tag}_sig_s{v}();")
         src.append(f"uint32_t fused_{S.tag}_sig_bwd();")
@@ -1672,8 +1775,9 @@ def main():
         sg = ", ".join([f"fused_{S.tag}_sig_s{v}()" for v in MODES] + [f"fused_{S.tag}_sig_bwd()"] * 2)
         st = ", ".join(f"fused_{S.tag}_kernel_s1t({k})" for k in range(4))
         su = ", ".join(f"fused_{S.tag}_kernel_s0u({k})" for k in range(4))
+        se = ", ".join(f"fused_{S.tag}_kernel_s7({k})" for k in range(4))
         src.append(f"        {{\"{S.tag}\", {S.M}, {S.N}, {S.Z}, {S.E}, {S.G}, {S.threads}, basegraph_{S.tag}, "
-                   f"{{{ks}}}, {{{kb}}}, {S.lanes_pad // 64}, {{{kt}}}, {{{sg}}}, {{{st}}}, {{{su}}}}},")
+                   f"{{{ks}}}, {{{kb}}}, {S.lanes_pad // 64}, {{{kt}}}, {{{sg}}}, {{{st}}}, {{{su}}}, {{{se}}}, fused_{S.tag}_sig_s7()}},")
     src.append("    };")
     src.append(f"    *n = {len(specs)};")
     src.append("    return tab;")

@@ -458,3 +458,99 @@ extern "C" int nldpc_ber_count(const float* llr, const uint8_t* y, int64_t B, in
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? NLDPC_OK : hip_fail(e, "ber_kernel launch");
 }
+
+// ---------------------------------------------------------------- parity-check syndrome weight
+// unsat[b] = number of the M*Z lifted check rows whose XOR of the hard decisions over the row's edges is 1 (edge
+// (i, j, s) joins check copy h to variable copy (h + s) mod Z).  One workgroup per codeword at a time: the hard
+// decisions go into an LDS bit array by wave ballots (coalesced reads, each LLR read once, four loads in flight per
+// thread), then each thread takes the parity of its check copies from the device edge tables.  A codeword whose
+// bits do not fit LDS (N*Z > 2^19) is read from global memory per edge instead.  done / T (the early-stopping
+// decode): a codeword with done[b] < T stopped on a zero syndrome, so its weight is 0 without reading it.
+namespace nldpc {
+constexpr int kSynMaxLdsBytes = 64 * 1024;
+
+__device__ __forceinline__ uint32_t hard_bit(float x, int convention) {
+    return convention == 0 ? (x > 0.f ? 1u : 0u) : (x < 0.f ? 1u : 0u);
+}
+
+__global__ __launch_bounds__(256) void syndrome_kernel(DevGraph G, const float* llr, int64_t B, int convention,
+                                                       int32_t* unsat, int use_lds, const int32_t* done, int32_t T) {
+    extern __shared__ uint32_t syn_bits[];
+    __shared__ int s_cnt;
+    const int NZ = G.N * G.Z, MZ = G.M * G.Z;
+    const int lane = threadIdx.x & 63;
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+        const float* row = llr + b * NZ;
+        if (done && done[b] < T) {  // (the same for the whole workgroup)
+            if (threadIdx.x == 0) unsat[b] = 0;
+            continue;
+        }
+        if (threadIdx.x == 0) s_cnt = 0;
+        if (use_lds) {
+            const int step = (int)blockDim.x;
+            for (int n0 = (int)threadIdx.x - lane; n0 < NZ; n0 += 4 * step) {  // (n0: the wave's first bit, wave-uniform)
+                float x[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int n = n0 + k * step + lane;
+                    x[k] = n < NZ ? row[n] : 0.f;  // (0 is bit 0 in either convention)
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int nk = n0 + k * step;
+                    if (nk < NZ) {
+                        const unsigned long long m = __ballot(hard_bit(x[k], convention));
+                        if (lane == 0) {
+                            syn_bits[nk >> 5] = (uint32_t)m;
+                            syn_bits[(nk >> 5) + 1] = (uint32_t)(m >> 32);
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        int cnt = 0;
+        for (int r = threadIdx.x; r < MZ; r += blockDim.x) {
+            const int i = r / G.Z, h = r - i * G.Z;
+            uint32_t par = 0;
+            for (int e = G.row_ptr[i]; e < G.row_ptr[i + 1]; ++e) {
+                int v = h + G.e_shift[e];
+                if (v >= G.Z) v -= G.Z;
+                const int n = G.e_var[e] * G.Z + v;
+                par ^= use_lds ? (syn_bits[n >> 5] >> (n & 31)) : hard_bit(row[n], convention);
+            }
+            cnt += (int)(par & 1u);
+        }
+        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+        if (lane == 0 && cnt) atomicAdd(&s_cnt, cnt);
+        __syncthreads();
+        if (threadIdx.x == 0) unsat[b] = s_cnt;
+        __syncthreads();  // (s_cnt and the bit array are rewritten for the next codeword)
+    }
+}
+}  // namespace nldpc
+
+namespace nldpc {
+int syndrome_run(const nldpc_graph* g, const float* llr, int64_t B, int32_t convention, int32_t* unsat,
+                 const int32_t* done, int32_t T, hipStream_t stream) {
+    if (!g || !llr || !unsat || B <= 0) return fail(NLDPC_EINVAL, "nldpc_syndrome: bad argument");
+    if (convention != 0 && convention != 1) return fail(NLDPC_EINVAL, "nldpc_syndrome: convention is 0 or 1");
+    const int64_t NZ = (int64_t)g->dev.N * g->dev.Z;
+    if (NZ >= (int64_t)1 << 31 || (int64_t)g->dev.M * g->dev.Z >= (int64_t)1 << 31)
+        return fail(NLDPC_EUNSUPPORTED, "nldpc_syndrome: codeword too long");
+    // the bit array: whole 64-bit ballots, so two words past the last full one
+    const size_t lds = (size_t)(((NZ + 63) >> 6) * 2 + 2) * sizeof(uint32_t);
+    const int use_lds = lds <= (size_t)kSynMaxLdsBytes ? 1 : 0;
+    const int64_t blocks = B < 262144 ? B : 262144;
+    DeviceGuard guard(g->device);
+    hipLaunchKernelGGL(syndrome_kernel, dim3((unsigned)blocks), dim3(256), use_lds ? lds : 0,
+                       stream, g->dev, llr, B, (int)convention, unsat, use_lds, done, T);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? NLDPC_OK : hip_fail(e, "syndrome_kernel launch");
+}
+}  // namespace nldpc
+
+extern "C" int nldpc_syndrome(const nldpc_graph* g, const float* llr, int64_t B, int32_t convention, int32_t* unsat,
+                              void* stream) {
+    return syndrome_run(g, llr, B, convention, unsat, nullptr, 0, static_cast<hipStream_t>(stream));
+}

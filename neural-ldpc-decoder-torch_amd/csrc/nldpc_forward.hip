@@ -275,7 +275,7 @@ SavedLayout saved_layout(const nldpc_graph* g, const nldpc_cfg* cfg, int64_t B, 
     return L;
 }
 
-// mode: 0 decode, 1 decode + save for backward, 2 / 3 count-only (the fused kernel variants)
+// mode: 0 decode, 1 decode + save for backward, 2 / 3 count-only, 8 early-stopping decode (the fused kernel variants)
 static bool fused_eligible(const nldpc_graph* g, const nldpc_cfg* cfg, int32_t T, int mode) {
     const bool saving = mode == 1;
     static const bool disabled = std::getenv("NLDPC_DISABLE_FUSED") != nullptr;
@@ -284,14 +284,18 @@ static bool fused_eligible(const nldpc_graph* g, const nldpc_cfg* cfg, int32_t T
     // int8 codes need one too; an inactive qbit decodes on the streaming kernels
     (void)saving;
     if (cfg->kind == NLDPC_QMS && !qms_active(cfg->qbit)) return false;
+    if (mode == 8 && (cfg->ucn || cfg->first_iter > 0)) return false;  // (the early stop has no UCN code and starts fresh)
     return fused_launch(g, mode, cfg->kind) && !cfg->c2v_in && T <= kFusedMaxT;
 }
 
 static int fused_forward(const nldpc_graph* g, const nldpc_cfg* cfg, int64_t B, int32_t T, const float* xa,
                          const float* w_cn, const float* w_ucn, const float* bias, const float* w_vn,
                          float* const* outs, const float* app_prev, float* c2v, void* saved, hipStream_t s,
-                         const uint8_t* cnt_y = nullptr, int32_t cnt_conv = 0, int64_t* counts = nullptr) {
-    const int mode = saved ? 1 : (counts ? ((cnt_y || cnt_conv) ? 3 : 2) : 0);
+                         const uint8_t* cnt_y = nullptr, int32_t cnt_conv = 0, int64_t* counts = nullptr,
+                         float* es_out = nullptr, int32_t* es_iters = nullptr) {
+    // (es_out: the early-stopping decode -- every iteration's posterior goes to that one buffer, the kernel freezes a
+    // codeword's part of it at t*; es_iters rides in the count-only pointer, which that kernel does not use)
+    const int mode = es_out ? 8 : saved ? 1 : (counts ? ((cnt_y || cnt_conv) ? 3 : 2) : 0);
     // (r6) a saving forward with one CN weight per iteration (NLDPC_FLAG_CN_TIED: sharing code 3, cfg5's NW(3,0,3)) and no
     // UCN runs the kernel specialised for it when the library has one: one scalar weight per iteration instead of a
     // per-edge row in SGPRs (the per-edge kernel spilled ~1 450 SGPRs), the UCN code not compiled
@@ -328,6 +332,10 @@ static int fused_forward(const nldpc_graph* g, const nldpc_cfg* cfg, int64_t B, 
     fa.cnt_y = cnt_y;
     fa.cnt_conv = cnt_conv;
     fa.cnt = reinterpret_cast<unsigned long long*>(counts);
+    if (es_out) {
+        for (int k = 0; k < T; ++k) fa.outs.p[k] = es_out;
+        fa.cnt = reinterpret_cast<unsigned long long*>(es_iters);
+    }
     if (saved) {
         const SavedLayout SL = saved_layout(g, cfg, B, T);
         char* sb = static_cast<char*>(saved);
@@ -373,8 +381,9 @@ extern "C" int nldpc_fast_path(const nldpc_graph* g, const nldpc_cfg* cfg, int64
     int st = validate_cfg(g, cfg, B, T);
     if (st) return st;
     if (!eligible) return fail(NLDPC_EINVAL, "nldpc_fast_path: null output");
-    if (saving < 0 || saving > 3) return fail(NLDPC_EINVAL, "nldpc_fast_path: saving is 0, 1 (or 2 / 3: count-only)");
-    *eligible = fused_eligible(g, cfg, T, saving) ? 1 : 0;
+    if (saving < 0 || saving > 4)
+        return fail(NLDPC_EINVAL, "nldpc_fast_path: saving is 0, 1 (or 2 / 3: count-only, 4: early stop)");
+    *eligible = fused_eligible(g, cfg, T, saving == 4 ? 8 : saving) ? 1 : 0;
     return NLDPC_OK;
 }
 
@@ -499,4 +508,31 @@ extern "C" int nldpc_forward_count(const nldpc_graph* g, const nldpc_cfg* cfg, i
     c.flags |= NLDPC_FLAG_NO_STATE;
     return fused_forward(g, &c, B, T, xa, w_cn, w_ucn, bias, w_vn, nullptr, nullptr, nullptr, nullptr,
                          static_cast<hipStream_t>(stream), y, convention, counts);
+}
+
+extern "C" int nldpc_forward_early_stop(const nldpc_graph* g, const nldpc_cfg* cfg, int64_t B, int32_t T, const float* xa,
+                                        const float* w_cn, const float* w_ucn, const float* bias, const float* w_vn,
+                                        float* out, int32_t* iters, int32_t* unsat, void* stream) {
+    int st = validate_cfg(g, cfg, B, T);
+    if (st) return st;
+    if (!xa || !out) return fail(NLDPC_EINVAL, "nldpc_forward_early_stop: xa and out are required");
+    if (cfg->kind == NLDPC_NEURAL && (!w_cn || !bias))
+        return fail(NLDPC_EINVAL, "nldpc_forward_early_stop: the Neural decoder needs w_cn and bias");
+    if (cfg->vn_cumulative && !w_vn) return fail(NLDPC_EINVAL, "nldpc_forward_early_stop: vn_cumulative needs w_vn");
+    if (cfg->c2v_in) return fail(NLDPC_EUNSUPPORTED, "nldpc_forward_early_stop: starts from a fresh message state (c2v_in == 0)");
+    if (cfg->first_iter > 0) return fail(NLDPC_EUNSUPPORTED, "nldpc_forward_early_stop: first_iter must be 0");
+    if (T > kFusedMaxT) return fail(NLDPC_EUNSUPPORTED, "nldpc_forward_early_stop: T <= 64");
+    if (!fused_eligible(g, cfg, T, 8))
+        return fail(NLDPC_EUNSUPPORTED, "nldpc_forward_early_stop: needs the fused path (a compiled base graph, no UCN, "
+                                        "no NLDPC_FLAG_STREAM, an active QMS quantiser); decode with nldpc_forward and "
+                                        "select with nldpc_syndrome instead");
+    DeviceGuard guard(g->device);
+    nldpc_cfg c = *cfg;
+    c.flags |= NLDPC_FLAG_NO_STATE;
+    (void)w_ucn;
+    st = fused_forward(g, &c, B, T, xa, w_cn, nullptr, bias, w_vn, nullptr, nullptr, nullptr, nullptr,
+                       static_cast<hipStream_t>(stream), nullptr, 0, nullptr, out, iters);
+    if (st || !unsat) return st;
+    // of the returned posterior, unsat(b, t*(b)): 0 for every codeword that stopped before T (the kernel skips them)
+    return syndrome_run(g, out, B, 0, unsat, iters, T, static_cast<hipStream_t>(stream));
 }

@@ -49,6 +49,7 @@ struct FusedArgs {
     const uint8_t* cnt_y;  // [B][N][Z] codeword bits (MODE 3), or nullptr (all-zero codeword, MODE 2)
     int32_t cnt_conv;      // 0: bit = LLR > 0; 1: bit = LLR < 0
     unsigned long long* cnt;  // [T][2] (+=) bit errors, frame errors
+                              // (the early-stopping decode, which counts nothing: int32 [B] iterations run, or nullptr)
     uint64_t* stamps;    // diagnostic stamp build only (make STAMPS=1): [256][waves][T][16] s_memtime
 };
 
@@ -704,13 +705,16 @@ struct FusedSpec {
                                // the generated kernel<KIND, 5>), or nullptr; built in the saving unit (sig[1])
     void* decode_ucnw[4];      // (r6) decode with UCN and CN / UCN / cumulative VN weights all given (MODE 7 in
                                // fused_launch; the generated kernel<KIND, 6>), or nullptr; built in the decode unit (sig[0])
+    void* early_stop[4];       // early-stopping decode (MODE 8 in fused_launch; the generated kernel<KIND, 7>), a unit of its own
+    uint32_t sig_early_stop;   // that unit's kFusedArgsSig
 };
 
 const FusedSpec* fused_specs(int* n);
 
 // How to launch the register-resident kernel of (graph, MODE, kind) (MODE 4: the backward; MODE 5: the
 // backward for tied weights; MODE 6: the saving forward for tied CN weights without UCN; MODE 7: the decode with UCN
-// and CN / UCN / cumulative VN weights -- MODES 5 to 7 library kernels only, a run-time compiled graph uses MODE 4 / 1): one compiled
+// and CN / UCN / cumulative VN weights; MODE 8: the early-stopping decode -- MODES 5 to 8 library kernels only, a run-time
+// compiled graph uses MODE 4 / 1 / 0 and takes the early stop's fallback in nldpc/decode.py): one compiled
 // into the library (fused_specs table, hipLaunchKernel) or one compiled at run time for this graph and
 // attached (nldpc_graph_attach_kernel, hipModuleLaunchKernel); empty when neither exists.
 struct FusedLaunch {

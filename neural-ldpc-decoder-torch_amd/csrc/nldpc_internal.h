@@ -91,6 +91,10 @@ struct SavedLayout {
 inline bool qms_active(int q) { return q == 6 || q == 5 || q == -5 || q == 4 || q == 3; }
 SavedLayout saved_layout(const nldpc_graph* g, const nldpc_cfg* cfg, int64_t B, int32_t T);
 int validate_cfg(const nldpc_graph* g, const nldpc_cfg* cfg, int64_t B, int32_t T);
+// nldpc_syndrome (nldpc_aux.hip); done / T: codewords with done[b] < T are known to have weight 0 (the early-stopping
+// decode's iteration counts) and are not read; done == nullptr: every codeword is read
+int syndrome_run(const nldpc_graph* g, const float* llr, int64_t B, int32_t convention, int32_t* unsat,
+                 const int32_t* done, int32_t T, hipStream_t stream);
 
 // benchmark instrumentation (nldpc_profile.cpp)
 enum ProfKind { PROF_VN = 0, PROF_CN = 1, PROF_POST = 2, PROF_FUSED = 3, PROF_VNB = 4, PROF_CNB = 5, PROF_FUSED_BWD = 6 };

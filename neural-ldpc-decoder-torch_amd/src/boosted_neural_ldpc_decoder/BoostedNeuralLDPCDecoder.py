@@ -36,7 +36,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from nldpc.decode import KIND_MS, KIND_QMS, KIND_SP, DecodeCfg, decode_autograd, decode_count
+from nldpc.decode import KIND_MS, KIND_QMS, KIND_SP, DecodeCfg, decode_autograd, decode_count, decode_early_stop
 
 from boosted_neural_ldpc_decoder.ConnectingMatrixTorch import ConnectingMatrixTorch
 from boosted_neural_ldpc_decoder.Functions import Functions
@@ -302,6 +302,23 @@ class BoostedNeuralLDPCDecoder(nn.Module):
                         llr_hi=float(self.allowed_llr_range.end), keep_state=False)
         return decode_count(self.conn_mat.graph, cfg, xa, T, w_cn=w_cn, w_ucn=w_ucn, w_vn=w_vn, y=y,
                             convention=convention)
+
+    @torch.no_grad()
+    def decode_early_stop(self, xa):
+        """Early-stopping decode (extension): every codeword stops at the first iteration of forward(xa) (target_iter
+        None, no fixed iterations) whose hard decision (LLR > 0) satisfies all parity checks.  Returns (out [B, N*Z]
+        = outputs[t*(b)][b], iters [B] int32 = t*(b) + 1, unsat [B] int32 = unsatisfied checks of out[b]; 0 = a
+        codeword), nldpc.decode.decode_early_stop; self.outputs / self.llr are not touched.  With UCN weights the
+        decode runs in full and the stopping iteration is selected afterwards (T posteriors of memory)."""
+        T = self.iter_node_counts
+        ws = [self._iteration_weights(it, [], None, 0, xa.device) for it in range(T)]
+        stack = lambda k: torch.stack([w[k] for w in ws]) if ws[0][k] is not None else None  # noqa: E731
+        w_cn, w_ucn, w_vn = stack(0), stack(1), stack(2)
+        qbit = self.decoder_qms_qbit if self.decoding_type == DecoderType.QMS else 0
+        cfg = DecodeCfg(kind=_KIND[self.decoding_type], qbit=qbit, ucn=w_ucn is not None,
+                        vn_cumulative=w_vn is not None, llr_lo=float(self.allowed_llr_range.start),
+                        llr_hi=float(self.allowed_llr_range.end), keep_state=False)
+        return decode_early_stop(self.conn_mat.graph, cfg, xa, T, w_cn=w_cn, w_ucn=w_ucn, w_vn=w_vn)
 
     # ------------------------------------------------------------------ forward
     def forward(self, xa, target_iter=None, fixed_iter=None, fixed_iter_weight=None):

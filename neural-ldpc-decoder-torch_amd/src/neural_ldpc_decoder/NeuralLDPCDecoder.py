@@ -10,7 +10,7 @@ registered (22.9 GB each at z=384); their keys in an old state_dict are accepted
 import torch
 import torch.nn as nn
 
-from nldpc.decode import KIND_NEURAL, DecodeCfg, decode_autograd, decode_count
+from nldpc.decode import KIND_NEURAL, DecodeCfg, decode_autograd, decode_count, decode_early_stop
 
 from .ConnectingMatrixTorch import ConnectingMatrixTorch
 
@@ -64,3 +64,12 @@ class NeuralLDPCDecoder(nn.Module):
         T = self.iter_node_counts
         w, b = self._weights()
         return decode_count(self.conn_mat.graph, self._cfg, xa, T, w_cn=w, bias=b, y=y, convention=convention)
+
+    @torch.no_grad()
+    def decode_early_stop(self, xa):
+        """Early-stopping decode (extension): every codeword stops at the first iteration whose hard decision
+        (LLR > 0) satisfies all parity checks.  Returns (out [B, N*Z] = forward(xa)[t*(b)][b], iters [B] int32 =
+        t*(b) + 1, unsat [B] int32 = unsatisfied checks of out[b]; 0 = a codeword), nldpc.decode.decode_early_stop."""
+        T = self.iter_node_counts
+        w, b = self._weights()
+        return decode_early_stop(self.conn_mat.graph, self._cfg, xa, T, w_cn=w, bias=b)

@@ -7,6 +7,7 @@ awgn_llr       codeword (all-zero or given y) over BPSK/AWGN, LLR = 2*((-1)^(1-y
 sigma_for      the reference's Eb/N0 -> sigma mapping with its code-rate formula (AWGNPassedDatagen.py:47-49).
 ber_counts     fused bit/frame error counters for a list of posteriors (Functions.evaluate_ber_fer,
                Functions.py:85-102) without 2T host synchronisations.
+syndrome_weight  unsatisfied parity checks of the hard decision of each posterior (is the output a codeword?).
 """
 from __future__ import annotations
 
@@ -71,3 +72,25 @@ def ber_counts(outputs, y: torch.Tensor | None = None, *, convention: int = 0) -
         _lib.check(L.nldpc_ber_count(o2.data_ptr(), None if yb is None else yb.data_ptr(), o2.shape[0], o2.shape[1],
                                      int(convention), counts[t].data_ptr(), s), "nldpc_ber_count")
     return counts
+
+
+def syndrome_weight(outputs, graph, *, convention: int = 0) -> torch.Tensor:
+    """int32 [T, B] device tensor: for each posterior in `outputs` (one [B, N*Z] / [B, N, Z] tensor or a list of
+    them) and each codeword, the number of the graph's M*Z lifted parity checks its hard decision leaves
+    unsatisfied (nldpc_syndrome).  0 = the hard decision is a codeword -- no transmitted bits needed.
+    convention 0: bit = (LLR > 0), the decoder's (an exact 0 is bit 0); 1: bit = (LLR < 0)."""
+    outputs = [outputs] if isinstance(outputs, torch.Tensor) else list(outputs)
+    dev = outputs[0].device
+    if dev.type != "cuda":
+        raise RuntimeError("syndrome_weight runs on the ROCm device (no CPU path)")
+    B = int(outputs[0].shape[0])
+    unsat = torch.empty((len(outputs), B), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    h = graph.handle(dev)
+    s = _lib.stream_of(dev)
+    for t, o in enumerate(outputs):
+        o2 = o.reshape(o.shape[0], -1).to(torch.float32).contiguous()
+        if o2.shape != (B, graph.N * graph.Z):
+            raise ValueError(f"every output must be [B, N*Z] = [{B}, {graph.N * graph.Z}], got {tuple(o.shape)}")
+        _lib.check(L.nldpc_syndrome(h, o2.data_ptr(), B, int(convention), unsat[t].data_ptr(), s), "nldpc_syndrome")
+    return unsat

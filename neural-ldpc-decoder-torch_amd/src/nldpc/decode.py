@@ -143,6 +143,54 @@ def decode_count(graph: LiftedGraph, cfg: DecodeCfg, xa: torch.Tensor, T: int, *
     return counts
 
 
+def decode_early_stop(graph: LiftedGraph, cfg: DecodeCfg, xa: torch.Tensor, T: int, *, w_cn=None, w_ucn=None, bias=None,
+                      w_vn=None):
+    """Early-stopping decode: each codeword stops at t*(b), the first of the T iterations whose hard decision
+    (LLR > 0) satisfies every parity check (T-1 if none does).  Returns (out [B, N*Z] = the posterior of iteration
+    t*(b), bit for bit what decode(...) returns there; iters [B] int32 = t*(b) + 1; unsat [B] int32 = the
+    unsatisfied checks of out[b], 0 = a codeword).
+
+    Honours cfg.path.  The fused early-stop kernel (nldpc_forward_early_stop) checks the parity inside the kernel
+    and a workgroup leaves as soon as its codewords have stopped; it exists for the library's compiled base graphs,
+    without UCN.  Every other call ("stream", UCN, a graph with no kernel or a run-time compiled one) falls back to
+    decode(...) with all T outputs, syndrome_weight over them and a device-side selection of t*: that needs the T
+    posteriors' memory (T * B * N*Z floats) and saves no time.  path="fused" raises instead of falling back."""
+    _require_device_tensor(xa, "xa")
+    if xa.dim() != 3 or xa.shape[1] != graph.N or xa.shape[2] != graph.Z:
+        raise ValueError(f"xa must be [B, {graph.N}, {graph.Z}], got {tuple(xa.shape)}")
+    if cfg.first_iter != 0:
+        raise ValueError("decode_early_stop starts at iteration 0 (cfg.first_iter == 0)")
+    dev = xa.device
+    B = int(xa.shape[0])
+    c = dataclasses.replace(cfg, cn_tied=False).c_struct(False)
+    c.flags |= _lib.FLAG_NO_STATE
+    L = _lib.lib()
+    h = graph.handle(dev)
+    fast = ctypes.c_int32(0)
+    _lib.check(L.nldpc_fast_path(h, ctypes.byref(c), B, T, 4, ctypes.byref(fast)), "nldpc_fast_path")
+    if not fast.value:
+        if cfg.path == "fused":
+            raise _lib.NldpcUnsupported("decode_early_stop: the fused early-stop kernel is not available for this call "
+                                        "(needs a compiled base graph, no UCN, T <= 64)")
+        from .channel import syndrome_weight
+        outs, _, _ = decode(graph, dataclasses.replace(cfg, keep_state=False), xa, T, w_cn=w_cn, w_ucn=w_ucn, bias=bias,
+                            w_vn=w_vn)
+        sw = syndrome_weight(list(outs), graph)  # [T, B]
+        ok = sw == 0
+        tstar = torch.where(ok.any(0), ok.to(torch.int32).argmax(0), torch.full((B,), T - 1, device=dev)).to(torch.int64)
+        out = outs.gather(0, tstar.view(1, B, 1).expand(1, B, outs.shape[2]))[0]
+        return out, (tstar + 1).to(torch.int32), sw.gather(0, tstar.view(1, B))[0]
+    out = torch.empty((B, graph.N * graph.Z), dtype=torch.float32, device=dev)
+    iters = torch.empty((B,), dtype=torch.int32, device=dev)
+    unsat = torch.empty((B,), dtype=torch.int32, device=dev)
+    xa_c = _f32c(xa)
+    w_cn, bias, w_vn = _f32c(w_cn), _f32c(bias), _f32c(w_vn)
+    _lib.check(L.nldpc_forward_early_stop(h, ctypes.byref(c), B, T, _lib.ptr(xa_c), _lib.ptr(w_cn), None, _lib.ptr(bias),
+                                          _lib.ptr(w_vn), out.data_ptr(), iters.data_ptr(), unsat.data_ptr(),
+                                          _lib.stream_of(dev)), "nldpc_forward_early_stop")
+    return out, iters, unsat
+
+
 def _honour_tied(cfg: DecodeCfg, w_cn) -> DecodeCfg:
     """cfg.cn_tied holds only for a w_cn whose rows are one repeated value by construction (an expand(): stride 0
     along the edges, as the drop-in module passes sharing code 3); any other w_cn gets the per-edge gradient
