@@ -267,6 +267,34 @@ int nldpc_channel_llr(float* xa, int64_t B, int64_t L, float sigma, uint64_t see
                       float puncture_value, int64_t shorten_start, int64_t shorten_end, float shorten_value,
                       void* stream);
 
+/* ---- systematic QC-LDPC encoder (additive to ABI 4): the codewords the channel, the count-only decode and the
+ *      error counters take as y.  The reference has one generator matrix (resources/gen_matrix_bg2_z16.txt, BG2
+ *      z=16 only; train/train_BoostedNeuralLDPCDecoder.py multiplies info bits by it); this encodes for any base
+ *      graph whose parity part can be solved by substitution, at any Z.  Info columns are the first K = N - M base
+ *      columns, parity columns the last M.
+ *   nldpc_encode_plan (host only, no device): the substitution order.  A parity column with one entry is solved
+ *      last from its own row; in the remaining core a row with one unsolved parity column solves it, and when none is
+ *      left the XOR of the unused core rows must leave exactly one monomial on the unsolved columns (5G BG1/BG2 and
+ *      802.16e: the weight-3 column).  Step s (M steps, sorted by dependency level step_level[s] in 0..*n_levels-1)
+ *      sets y[step_col[s]][(h + step_shift[s]) mod Z] to the XOR over its terms k in step_ptr[s]..step_ptr[s+1] of
+ *      y[term_col[k]][(h + term_shift[k]) mod Z], for every check copy h; every term column is an info column or the
+ *      target of a step of a lower level; all degree-1 columns share one level.
+ *      step_col / step_shift / step_level host [M], step_ptr host [M+1], term_col / term_shift host [term_cap].
+ *      NLDPC_EUNSUPPORTED: the graph has no such order; NLDPC_EINVAL: term_cap too small (2 * E always suffices).
+ *   nldpc_encode: info [B][K*Z] uint8 (any non-zero byte is 1) -> y [B][N*Z] uint8 0/1, y[b][0..K*Z) = the info bits
+ *      and every parity check of y[b] satisfied.  info == NULL: the info bits come from Philox-4x32-10: with
+ *      c = b_offset + b and W = ceil(K*Z / 128), bit i of codeword c is bit (i & 31) of output word (i >> 5) & 3 at
+ *      counter (lo32(c*W + (i >> 7)), hi32(c*W + (i >> 7)), 0x454E4331, 0), key (lo32(seed), hi32(seed)) -- the
+ *      noise stream of nldpc_channel_llr has 0 in counter word 2 --, so a sharded batch draws the words of the
+ *      unsharded one.  One kernel over the plan's device tables, which nldpc_graph_create builds; stream-ordered,
+ *      no synchronisation, no allocation.  NLDPC_EUNSUPPORTED: the graph has no plan, or N*Z bytes do not fit the
+ *      kernel's LDS image. */
+int nldpc_encode_plan(int32_t M, int32_t N, int32_t Z, const int32_t* basegraph, int32_t* step_col,
+                      int32_t* step_shift, int32_t* step_level, int32_t* step_ptr, int32_t* term_col,
+                      int32_t* term_shift, int32_t term_cap, int32_t* n_levels);
+int nldpc_encode(const nldpc_graph* g, const uint8_t* info, int64_t B, uint64_t seed, int64_t b_offset, uint8_t* y,
+                 void* stream);
+
 /* ---- benchmark instrumentation: per-kernel HIP-event timing of nldpc_forward / nldpc_backward
  *   launches.  nldpc_profile_begin arms a recorder for up to `capacity` launches (not thread-safe);
  *   nldpc_profile_end synchronises on the recorded events and returns summed milliseconds and

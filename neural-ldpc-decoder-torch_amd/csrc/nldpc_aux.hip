@@ -4,6 +4,8 @@
 //   nldpc_bce_loss / nldpc_bce_grad  the multi-iteration BCE training loss and its gradient
 //                    (LDPCDecoderLoss.py:70-108), one pass over all T outputs each
 //   nldpc_hbm_probe  the measured HBM ceilings the bench's roofline quotes beside the 8 TB/s spec
+//   nldpc_syndrome   parity-check syndrome weight of a posterior's hard decision
+//   nldpc_encode     systematic QC-LDPC encoder: info bits (given or Philox-drawn) -> codeword bits (F6)
 #include <hip/hip_runtime.h>
 
 #include "nldpc_internal.h"
@@ -553,4 +555,183 @@ int syndrome_run(const nldpc_graph* g, const float* llr, int64_t B, int32_t conv
 extern "C" int nldpc_syndrome(const nldpc_graph* g, const float* llr, int64_t B, int32_t convention, int32_t* unsat,
                               void* stream) {
     return syndrome_run(g, llr, B, convention, unsat, nullptr, 0, static_cast<hipStream_t>(stream));
+}
+
+// ---------------------------------------------------------------- systematic encoder (nldpc_encode)
+// A workgroup encodes G codewords at a time (G a power of two, so that one step's G * Z work items fill the workgroup
+// at small Z; bounded by LDS), grid-stride over the groups.  The codewords live in LDS as bytes in the output layout,
+// [G][N*Z], placed so that LDS and global addresses agree mod 16: the info bytes are loaded (4 per lane) or expanded
+// from Philox words, the plan (EncTables, copied to LDS once) runs level by level with one barrier each -- a work item
+// is (step, codeword, 4 check copies h): it XORs its terms' bytes and writes the target bytes at the rotated copies --, and
+// the G * N * Z bytes leave with 16-byte loads and stores.
+namespace nldpc {
+constexpr int kEncThreads = 256;
+constexpr int kEncMaxLds = 64 * 1024;    // one workgroup's dynamic LDS
+constexpr int kEncGroupLds = 32 * 1024;  // G > 1 only while a workgroup stays below this (5 workgroups per CU)
+constexpr uint32_t kEncTag = 0x454E4331u;  // counter word 2 of the info-bit stream ("ENC1"; the noise stream has 0)
+
+struct EncArgs {
+    const uint32_t* words;  // EncTables
+    int32_t n_words, tab_words, rnd_words, n_levels, M;
+    int32_t Z, NZ, KZ, W, logG;
+    float rZq, rKZ, rW;  // reciprocals for enc_divmod (Zq = ceil(Z / 4))
+    const uint8_t* info;
+    uint8_t* y;
+    int64_t B, b_offset;
+    uint64_t seed;
+};
+
+// it / d and it % d for it < 2^22 and rd = 1.0f / d: the float quotient is off by at most one
+__device__ __forceinline__ void enc_divmod(uint32_t it, uint32_t d, float rd, uint32_t& q, uint32_t& r) {
+    q = (uint32_t)((float)it * rd);
+    int32_t rr = (int32_t)(it - q * d);
+    if (rr < 0) {
+        q--;
+        rr += (int32_t)d;
+    } else if (rr >= (int32_t)d) {
+        q++;
+        rr -= (int32_t)d;
+    }
+    r = (uint32_t)rr;
+}
+
+__global__ __launch_bounds__(kEncThreads) void encode_kernel(EncArgs a) {
+    extern __shared__ uint4 enc_lds[];
+    uint32_t* tab = reinterpret_cast<uint32_t*>(enc_lds);
+    uint32_t* rnd = tab + a.tab_words;                               // [G][W][4] Philox words (info == nullptr)
+    uint8_t* img0 = reinterpret_cast<uint8_t*>(rnd + a.rnd_words);  // 16-byte aligned; [pad < 16][G][N*Z]
+    const uint32_t tid = threadIdx.x, nt = blockDim.x;
+    for (uint32_t i = tid; i < (uint32_t)a.n_words; i += nt) tab[i] = a.words[i];
+    const uint32_t* lvl_ptr = tab;
+    const uint32_t* step_ptr = lvl_ptr + a.n_levels + 1;
+    const uint32_t* step_tgt = step_ptr + a.M + 1;
+    const uint32_t* term = step_tgt + a.M;
+    const uint32_t Z = (uint32_t)a.Z, NZ = (uint32_t)a.NZ, KZ = (uint32_t)a.KZ, W = (uint32_t)a.W;
+    const uint32_t G = 1u << a.logG, Zq = (Z + 3) >> 2;  // a work item: 4 check copies of one step and codeword
+    const int64_t ngroups = (a.B + G - 1) >> a.logG;
+    for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+        const int64_t b0 = grp << a.logG;
+        const uint32_t gc = a.B - b0 < (int64_t)G ? (uint32_t)(a.B - b0) : G;  // codewords of this group
+        uint8_t* yg = a.y + b0 * NZ;
+        const uint32_t pad = (uint32_t)(reinterpret_cast<uintptr_t>(yg) & 15);
+        uint8_t* img = img0 + pad;
+        if (a.info) {
+            // the group's gc * KZ info bytes are contiguous: the aligned dwords that cover them, 4 bytes per lane
+            const uint8_t* src = a.info + b0 * KZ;
+            const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(src) & 3), n = gc * KZ;
+            const uint32_t* src4 = reinterpret_cast<const uint32_t*>(src - mis);
+            for (uint32_t w = tid; w < (mis + n + 3) >> 2; w += nt) {
+                const uint32_t v = src4[w];
+                int32_t idx = (int32_t)(4 * w) - (int32_t)mis;  // info byte of the dword's byte 0 (< 0: before the group)
+                uint32_t cw = 0, i = 0;
+                if (idx > 0) enc_divmod((uint32_t)idx, KZ, a.rKZ, cw, i);
+#pragma unroll
+                for (int k = 0; k < 4; ++k, ++idx) {
+                    if (idx < 0 || idx >= (int32_t)n) continue;
+                    img[cw * NZ + i] = ((v >> (8 * k)) & 0xFFu) ? 1 : 0;
+                    if (++i == KZ) {
+                        i = 0;
+                        ++cw;
+                    }
+                }
+            }
+        } else {
+            for (uint32_t it = tid; it < gc * W; it += nt) {
+                uint32_t cw, k;
+                enc_divmod(it, W, a.rW, cw, k);
+                const uint64_t ctr = (uint64_t)(a.b_offset + b0 + cw) * W + k;
+                const U4 r = philox4x32_10(U4{(uint32_t)ctr, (uint32_t)(ctr >> 32), kEncTag, 0u}, (uint32_t)a.seed,
+                                           (uint32_t)(a.seed >> 32));
+                reinterpret_cast<uint4*>(rnd)[it] = make_uint4(r.x, r.y, r.z, r.w);
+            }
+            __syncthreads();
+            for (uint32_t it = tid; it < gc * KZ; it += nt) {
+                uint32_t cw, i;
+                enc_divmod(it, KZ, a.rKZ, cw, i);
+                img[cw * NZ + i] = (uint8_t)((rnd[cw * 4 * W + (i >> 5)] >> (i & 31)) & 1u);
+            }
+        }
+        __syncthreads();  // (the first time round also: the plan is in LDS)
+        for (int l = 0; l < a.n_levels; ++l) {
+            const uint32_t s0 = lvl_ptr[l], nitems = ((lvl_ptr[l + 1] - s0) << a.logG) * Zq;
+            for (uint32_t it = tid; it < nitems; it += nt) {
+                uint32_t q, hq;
+                enc_divmod(it, Zq, a.rZq, q, hq);
+                const uint32_t cw = q & (G - 1), s = s0 + (q >> a.logG);
+                if (cw >= gc) continue;
+                uint8_t* c = img + cw * NZ;
+                uint32_t h[4], acc[4] = {0, 0, 0, 0};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) h[k] = min(4 * hq + k, Z - 1);  // (past Z: the last copy again, not written)
+                for (uint32_t p = step_ptr[s]; p < step_ptr[s + 1]; ++p) {
+                    const uint32_t t = term[p];
+                    const uint8_t* col = c + (t >> 16);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const uint32_t v = h[k] + (t & 0xFFFFu);
+                        acc[k] ^= col[min(v, v - Z)];  // (h + shift) mod Z
+                    }
+                }
+                const uint32_t t = step_tgt[s];
+                uint8_t* col = c + (t >> 16);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t v = h[k] + (t & 0xFFFFu);
+                    if (4 * hq + k < Z) col[min(v, v - Z)] = (uint8_t)acc[k];
+                }
+            }
+            __syncthreads();
+        }
+        // gc * NZ bytes out: bytes up to the first 16-byte boundary, 16 bytes per lane, the bytes after the last
+        const uint32_t n = gc * NZ, head = min((16u - pad) & 15u, n), body = (n - head) >> 4;
+        if (tid < head) yg[tid] = img[tid];
+        uint4* dst = reinterpret_cast<uint4*>(yg + head);
+        const uint4* src = reinterpret_cast<const uint4*>(img + head);
+        for (uint32_t i = tid; i < body; i += nt) dst[i] = src[i];
+        const uint32_t done = head + 16 * body;
+        if (tid < n - done) yg[done + tid] = img[done + tid];
+        __syncthreads();  // (the image is rewritten for the next group)
+    }
+}
+}  // namespace nldpc
+
+extern "C" int nldpc_encode(const nldpc_graph* g, const uint8_t* info, int64_t B, uint64_t seed, int64_t b_offset,
+                            uint8_t* y, void* stream) {
+    if (!g || !y || B <= 0 || b_offset < 0) return fail(NLDPC_EINVAL, "nldpc_encode: bad argument");
+    const EncTables& t = g->enc;
+    if (!t.words) return fail(NLDPC_EUNSUPPORTED, std::string("nldpc_encode: ") + (t.why ? t.why : "no plan"));
+    const int64_t Z = g->dev.Z, NZ = (int64_t)g->dev.N * Z, KZ = (int64_t)(g->dev.N - g->dev.M) * Z, W = (KZ + 127) / 128;
+    EncArgs a{};
+    a.words = t.words;
+    a.n_words = t.n_words;
+    a.tab_words = (t.n_words + 3) & ~3;
+    a.n_levels = t.n_levels;
+    a.M = g->dev.M;
+    a.Z = (int32_t)Z;
+    a.NZ = (int32_t)NZ;
+    a.KZ = (int32_t)KZ;
+    a.W = (int32_t)W;
+    a.rZq = 1.0f / (float)((Z + 3) / 4);
+    a.rKZ = 1.0f / (float)KZ;
+    a.rW = 1.0f / (float)W;
+    a.info = info;
+    a.y = y;
+    a.B = B;
+    a.b_offset = b_offset;
+    a.seed = seed;
+    // LDS: the plan, then per codeword its image and (Philox info) its 4 * W words, then the 16 alignment bytes
+    const int64_t fixed = (int64_t)a.tab_words * 4 + 16, per_cw = NZ + (info ? 0 : 16 * W);
+    if (fixed + per_cw > kEncMaxLds) return fail(NLDPC_EUNSUPPORTED, "nldpc_encode: the codeword image does not fit LDS");
+    int logG = 0;  // G: the smallest power of two whose G * ceil(Z / 4) items of one step fill the workgroup
+    while ((((int64_t)(Z + 3) / 4) << logG) < kEncThreads && ((int64_t)2 << logG) <= B && fixed + (per_cw << (logG + 1)) <= kEncGroupLds)
+        ++logG;
+    a.logG = logG;
+    a.rnd_words = info ? 0 : (int32_t)((4 * W) << logG);
+    const size_t lds = (size_t)(fixed + (per_cw << logG));
+    const int64_t groups = (B + ((int64_t)1 << logG) - 1) >> logG;
+    const int64_t blocks = groups < 262144 ? groups : 262144;
+    DeviceGuard guard(g->device);
+    hipLaunchKernelGGL(encode_kernel, dim3((unsigned)blocks), dim3(kEncThreads), lds, static_cast<hipStream_t>(stream), a);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? NLDPC_OK : hip_fail(e, "encode_kernel launch");
 }

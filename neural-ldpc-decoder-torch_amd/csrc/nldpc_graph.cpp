@@ -133,11 +133,195 @@ static void sp_plans(int M, int E, const std::vector<int32_t>& chk, const std::v
     }
 }
 
+// ---- systematic encoder plan (nldpc_encode_plan).  Info columns are the first K = N - M base columns, parity
+// columns the last M.  The parity part of both resource graphs is a small core (one weight-3 column and a dual
+// diagonal) plus, for BG2, degree-1 extension columns, so the parity blocks follow from the info blocks by
+// substitution in the circulant domain -- no inverse, nothing of size (M*Z)^2:
+//   * a parity column with exactly one entry is an extension column, solved last from its own row;
+//   * in the core (the other rows and parity columns) any row with exactly one unsolved parity column solves it;
+//   * when no such row is left, the XOR of all unused core rows must cancel every monomial on the unsolved columns but
+//     one, whose column it solves (the weight-3 column: its two equal shifts cancel, the dual diagonal cancels).
+// Step s: y[col][(h + shift) mod Z] = XOR over its terms of y[tcol][(h + tshift) mod Z] for every check copy h.
+// A step's level is one more than the highest level among its term columns (info columns: none); every extension
+// column takes the level after the core's last, so they run concurrently.  Steps are sorted by level.
+struct EncPlan {
+    std::vector<int32_t> col, shift, level, ptr, tcol, tshift;
+    int32_t n_levels = 0;
+};
+
+static bool encode_plan(int M, int N, int Z, const int32_t* hb, EncPlan& p, std::string& why) {
+    const int K = N - M;
+    if (K <= 0) return why = "no info columns (N <= M)", false;
+    struct Mono { int32_t col, shift; };
+    std::vector<std::vector<Mono>> rows(M);
+    std::vector<int32_t> cnt(N, 0), only_row(N, -1);
+    for (int i = 0; i < M; ++i)
+        for (int j = 0; j < N; ++j) {
+            const int32_t v = hb[(int64_t)i * N + j];
+            if (v < 0) continue;
+            rows[i].push_back(Mono{j, v % Z});
+            cnt[j]++;
+            only_row[j] = i;
+        }
+    // extension columns and their rows
+    std::vector<int32_t> ext_of_row(M, -1);
+    int n_core = 0;
+    for (int j = K; j < N; ++j) {
+        if (cnt[j] == 0) return why = "a parity column without entries", false;
+        if (cnt[j] != 1) { n_core++; continue; }
+        if (ext_of_row[only_row[j]] >= 0) return why = "two degree-1 parity columns in one row", false;
+        ext_of_row[only_row[j]] = j;
+    }
+    int core_rows = 0;
+    for (int i = 0; i < M; ++i) core_rows += ext_of_row[i] < 0;
+    if (core_rows != n_core) return why = "the core of the parity part is not square", false;
+
+    std::vector<int32_t> lvl(N, -1);  // level of the step that solves a column; info columns stay -1
+    std::vector<char> solved(N, 0), used(M, 0);
+    for (int j = 0; j < K; ++j) solved[j] = 1;
+    struct Step { int32_t col, shift, level; std::vector<Mono> terms; };
+    std::vector<Step> steps;
+    auto emit = [&](int32_t col, int32_t shift, std::vector<Mono> terms) {
+        int32_t l = 0;
+        for (const Mono& t : terms) l = std::max(l, lvl[t.col] + 1);
+        lvl[col] = l;
+        solved[col] = 1;
+        steps.push_back(Step{col, shift, l, std::move(terms)});
+    };
+    int left = n_core;
+    while (left > 0) {
+        bool progress = false;
+        for (int i = 0; i < M; ++i) {
+            if (used[i] || ext_of_row[i] >= 0) continue;
+            int unk = 0, at = -1;
+            for (size_t k = 0; k < rows[i].size(); ++k)
+                if (!solved[rows[i][k].col]) { unk++; at = (int)k; }
+            if (unk != 1) continue;
+            std::vector<Mono> terms;
+            for (size_t k = 0; k < rows[i].size(); ++k)
+                if ((int)k != at) terms.push_back(rows[i][k]);
+            emit(rows[i][at].col, rows[i][at].shift, std::move(terms));
+            used[i] = 1;
+            left--;
+            progress = true;
+        }
+        if (progress || left == 0) continue;
+        // stuck: the XOR of the unused core rows, equal monomials cancelling in pairs
+        std::vector<Mono> sum;
+        for (int i = 0; i < M; ++i) {
+            if (used[i] || ext_of_row[i] >= 0) continue;
+            for (const Mono& m : rows[i]) {
+                auto it = std::find_if(sum.begin(), sum.end(), [&](const Mono& q) { return q.col == m.col && q.shift == m.shift; });
+                if (it == sum.end()) sum.push_back(m);
+                else sum.erase(it);
+            }
+        }
+        int unk = 0, at = -1;
+        for (size_t k = 0; k < sum.size(); ++k)
+            if (!solved[sum[k].col]) { unk++; at = (int)k; }
+        if (unk != 1) return why = "the sum of the core rows leaves " + std::to_string(unk) + " monomials on the unsolved parity columns (need exactly 1)", false;
+        const Mono tgt = sum[at];
+        sum.erase(sum.begin() + at);
+        std::sort(sum.begin(), sum.end(), [](const Mono& a, const Mono& b) { return a.col != b.col ? a.col < b.col : a.shift < b.shift; });
+        emit(tgt.col, tgt.shift, std::move(sum));
+        left--;
+    }
+    int32_t ext_level = 0;
+    for (const Step& s : steps) ext_level = std::max(ext_level, s.level + 1);
+    for (int i = 0; i < M; ++i) {
+        const int j = ext_of_row[i];
+        if (j < 0) continue;
+        std::vector<Mono> terms;
+        int32_t shift = 0;
+        for (const Mono& m : rows[i]) {
+            if (m.col == j) { shift = m.shift; continue; }
+            if (!solved[m.col]) return why = "two unknown parity columns in an extension row", false;
+            terms.push_back(m);
+        }
+        steps.push_back(Step{j, shift, ext_level, std::move(terms)});
+    }
+    for (int i = 0; i < M; ++i)  // (extension columns count as solved only now: no extension row may use another's)
+        if (ext_of_row[i] >= 0) solved[ext_of_row[i]] = 1;
+    std::stable_sort(steps.begin(), steps.end(), [](const Step& a, const Step& b) { return a.level < b.level; });
+    p = EncPlan{};
+    p.ptr.push_back(0);
+    for (const Step& s : steps) {
+        p.col.push_back(s.col);
+        p.shift.push_back(s.shift);
+        p.level.push_back(s.level);
+        for (const Mono& t : s.terms) {
+            p.tcol.push_back(t.col);
+            p.tshift.push_back(t.shift);
+        }
+        p.ptr.push_back((int32_t)p.tcol.size());
+        p.n_levels = std::max(p.n_levels, s.level + 1);
+    }
+    return true;
+}
+
+// the plan in the encode kernel's packed form (EncTables), on the graph's device
+static int encode_tables(nldpc_graph* g, int M, int N, int Z, const int32_t* hb) {
+    EncPlan p;
+    std::string why;
+    g->enc = EncTables{nullptr, 0, 0, 0, "the parity part of the base graph has no substitution order"};
+    if (!encode_plan(M, N, Z, hb, p, why)) return NLDPC_OK;  // (nldpc_encode_plan says why)
+    if ((int64_t)N * Z > kEncMaxImage) {
+        g->enc.why = "the codeword image does not fit LDS";
+        return NLDPC_OK;
+    }
+    std::vector<uint32_t> w;
+    int s = 0;
+    for (int l = 0; l <= p.n_levels; ++l) {  // lvl_ptr
+        while (s < M && p.level[s] < l) ++s;
+        w.push_back((uint32_t)s);
+    }
+    for (int32_t v : p.ptr) w.push_back((uint32_t)v);
+    for (int k = 0; k < M; ++k) w.push_back((uint32_t)(p.col[k] * Z) << 16 | (uint32_t)p.shift[k]);
+    for (size_t k = 0; k < p.tcol.size(); ++k) w.push_back((uint32_t)(p.tcol[k] * Z) << 16 | (uint32_t)p.tshift[k]);
+    void* d = nullptr;
+    NLDPC_HIP_CHECK(hipMalloc(&d, w.size() * sizeof(uint32_t)));
+    hipError_t e = hipMemcpy(d, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return hip_fail(e, "hipMemcpy(encoder tables)");
+    }
+    g->enc = EncTables{static_cast<const uint32_t*>(d), (int32_t)w.size(), p.n_levels, (int32_t)p.tcol.size(), nullptr};
+    return NLDPC_OK;
+}
+
 }  // namespace nldpc
 
 using namespace nldpc;
 
 extern "C" int nldpc_abi_version(void) { return NLDPC_ABI_VERSION; }
+
+extern "C" int nldpc_encode_plan(int32_t M, int32_t N, int32_t Z, const int32_t* basegraph, int32_t* step_col,
+                                 int32_t* step_shift, int32_t* step_level, int32_t* step_ptr, int32_t* term_col,
+                                 int32_t* term_shift, int32_t term_cap, int32_t* n_levels) {
+    try {
+        if (!basegraph || !step_col || !step_shift || !step_level || !step_ptr || !term_col || !term_shift || !n_levels)
+            return fail(NLDPC_EINVAL, "nldpc_encode_plan: null pointer");
+        if (M <= 0 || N <= 0 || Z <= 0) return fail(NLDPC_EINVAL, "nldpc_encode_plan: M, N, Z must be positive");
+        for (int64_t q = 0; q < (int64_t)M * N; ++q)
+            if (basegraph[q] < -1) return fail(NLDPC_EINVAL, "nldpc_encode_plan: base graph entries must be >= -1");
+        EncPlan p;
+        std::string why;
+        if (!encode_plan(M, N, Z, basegraph, p, why)) return fail(NLDPC_EUNSUPPORTED, "nldpc_encode_plan: no plan: " + why);
+        if ((int64_t)p.tcol.size() > term_cap)
+            return fail(NLDPC_EINVAL, "nldpc_encode_plan: term_cap too small (" + std::to_string(p.tcol.size()) +
+                                          " terms; twice the number of edges always suffices)");
+        std::copy(p.col.begin(), p.col.end(), step_col);
+        std::copy(p.shift.begin(), p.shift.end(), step_shift);
+        std::copy(p.level.begin(), p.level.end(), step_level);
+        std::copy(p.ptr.begin(), p.ptr.end(), step_ptr);
+        std::copy(p.tcol.begin(), p.tcol.end(), term_col);
+        std::copy(p.tshift.begin(), p.tshift.end(), term_shift);
+        *n_levels = p.n_levels;
+        return NLDPC_OK;
+    } catch (...) {
+        return fail(NLDPC_EINVAL, "nldpc_encode_plan: host allocation failed");
+    }
+}
 
 extern "C" const char* nldpc_last_error(void) { return g_last_error.c_str(); }
 
@@ -237,6 +421,10 @@ extern "C" int nldpc_graph_create(int32_t M, int32_t N, int32_t Z, const int32_t
         std::memcpy(g->h_chk, chk.data(), E * sizeof(int32_t));
         std::memcpy(g->h_var, var.data(), E * sizeof(int32_t));
         std::memcpy(g->h_shift, shift.data(), E * sizeof(int32_t));
+        if (int rc = encode_tables(g, M, N, Z, basegraph)) {  // (a graph without a plan is still a graph)
+            nldpc_graph_destroy(g);
+            return rc;
+        }
         *out = g;
         return NLDPC_OK;
     } catch (const std::bad_alloc&) {
@@ -407,6 +595,7 @@ extern "C" int nldpc_graph_destroy(nldpc_graph* g) {
     {
         DeviceGuard guard(g->device);
         if (g->blob) (void)hipFree(g->blob);
+        if (g->enc.words) (void)hipFree(const_cast<uint32_t*>(g->enc.words));
         for (auto& row : g->jit_mod)
             for (hipModule_t m : row)
                 if (m) (void)hipModuleUnload(m);

@@ -41,6 +41,22 @@ TanhRef tanh_ref_table(int device);
 
 }  // namespace nldpc
 
+namespace nldpc {
+// The systematic encoder's plan (nldpc_encode_plan) as the encode kernel reads it: one device allocation of
+// 32-bit words, copied to LDS by every workgroup.
+//   lvl_ptr [n_levels+1]  steps of dependency level l are lvl_ptr[l] .. lvl_ptr[l+1]
+//   step_ptr [M+1]        terms of step s are step_ptr[s] .. step_ptr[s+1]
+//   step_tgt [M], term [n_terms]   (column * Z) << 16 | shift: the byte offset of the column in a codeword's
+//                         [N][Z] image and the rotation (both below 2^16: the image has to fit LDS anyway)
+// words == nullptr: the graph has no plan, or its codeword is too long for the packed form (why says which).
+struct EncTables {
+    const uint32_t* words;
+    int32_t n_words, n_levels, n_terms;
+    const char* why;
+};
+constexpr int64_t kEncMaxImage = 65535;  // N*Z bytes of one codeword
+}  // namespace nldpc
+
 struct nldpc_graph {
     nldpc::DevGraph dev;
     int32_t device;
@@ -55,6 +71,7 @@ struct nldpc_graph {
     int32_t* h_chk;
     int32_t* h_var;
     int32_t* h_shift;
+    nldpc::EncTables enc;  // the encoder's device tables (nldpc_encode), built with the graph
 };
 
 namespace nldpc {

@@ -29,13 +29,13 @@ EXPORTED = (
     "nldpc_graph_edges", "nldpc_graph_attach_kernel", "nldpc_graph_kernels", "nldpc_fast_path", "nldpc_saved_bytes", "nldpc_forward", "nldpc_backward_workspace", "nldpc_backward", "nldpc_ber_count",
     "nldpc_awgn_llr", "nldpc_profile_begin", "nldpc_profile_end", "nldpc_bce_workspace", "nldpc_bce_loss",
     "nldpc_bce_grad", "nldpc_bce_loss_grad", "nldpc_bce_grad_unless_unit", "nldpc_forward_count", "nldpc_channel_llr", "nldpc_hbm_probe",
-    "nldpc_code_object_sig", "nldpc_syndrome", "nldpc_forward_early_stop",
+    "nldpc_code_object_sig", "nldpc_syndrome", "nldpc_forward_early_stop", "nldpc_encode_plan", "nldpc_encode",
 )
 
 
 # entries added after the ABI 4 structs were fixed (no layout change): optional in older builds
 _ADDED_IN_ABI4 = ("nldpc_bce_loss_grad", "nldpc_bce_grad_unless_unit", "nldpc_code_object_sig", "nldpc_syndrome",
-                  "nldpc_forward_early_stop")
+                  "nldpc_forward_early_stop", "nldpc_encode_plan", "nldpc_encode")
 
 
 class NldpcCfg(ctypes.Structure):
@@ -95,6 +95,8 @@ def _declare(lib):
         "nldpc_syndrome": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
         "nldpc_forward_early_stop": (_i32, [_vp, ctypes.POINTER(NldpcCfg), _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp]),
+        "nldpc_encode_plan": (_i32, [_i32, _i32, _i32] + [ctypes.POINTER(_i32)] * 7 + [_i32, ctypes.POINTER(_i32)]),
+        "nldpc_encode": (_i32, [_vp, _vp, _i64, ctypes.c_uint64, _i64, _vp, _vp]),
         "nldpc_awgn_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp]),
         "nldpc_channel_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp, _i64, _i64,
                                      ctypes.c_float, _i64, _i64, ctypes.c_float, _vp]),

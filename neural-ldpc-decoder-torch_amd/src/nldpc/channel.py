@@ -4,6 +4,8 @@ awgn_llr       codeword (all-zero or given y) over BPSK/AWGN, LLR = 2*((-1)^(1-y
                reference's QMS quantiser, puncturing and shortening; n from Philox-4x32-10 at
                counter (b_offset + b)*L + k: a batch sharded over ranks draws exactly the noise of the
                unsharded batch (replaces the numpy per-codeword loop of AWGNPassedDatagen.py:75-193).
+encode         systematic QC-LDPC encoder (nldpc_encode): given or Philox-drawn info bits -> codeword bits y, the
+               input awgn_llr, ber_counts and count_errors take (the reference has a generator matrix for BG2 z=16 only).
 sigma_for      the reference's Eb/N0 -> sigma mapping with its code-rate formula (AWGNPassedDatagen.py:47-49).
 ber_counts     fused bit/frame error counters for a list of posteriors (Functions.evaluate_ber_fer,
                Functions.py:85-102) without 2T host synchronisations.
@@ -49,6 +51,39 @@ def awgn_llr(B: int, N: int, Z: int, sigma: float, *, seed: int = 2042, b_offset
                                             int(b_offset), int(qbit), _lib.ptr(yb), int(p0), int(p1),
                                             float(puncture_value), int(s0), int(s1), float(shortening_value),
                                             _lib.stream_of(out.device)), "nldpc_channel_llr")
+    return out
+
+
+def encode(graph, info: torch.Tensor | None = None, *, B: int | None = None, seed: int = 2042, b_offset: int = 0,
+           device=None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """uint8 [B, N*Z] codewords (values 0 / 1) of `graph` on the device: y[:, :K*Z] are the info bits, and every parity
+    check of y is satisfied (nldpc_encode; raises NldpcUnsupported for a graph without an encode plan).
+    info: [B, K*Z] bits of any dtype on the device (!= 0 counts as 1), or None: B codewords whose info bits are drawn
+    on the device from Philox-4x32-10(seed) at codeword index b_offset + b -- a batch sharded over ranks draws the
+    words of the unsharded batch (the stream is the one include/nldpc.h states, apart from the noise of awgn_llr)."""
+    KZ, L = graph.K * graph.Z, graph.N * graph.Z
+    ib = None
+    if info is not None:
+        device = info.device
+        if info.dim() != 2 or info.shape[1] != KZ or (B is not None and B != info.shape[0]):
+            raise ValueError(f"info must be a [B, K*Z] = [{'B' if B is None else B}, {KZ}] tensor")
+        B = int(info.shape[0])
+        ib = info.contiguous() if info.dtype == torch.uint8 else (info != 0).to(torch.uint8).contiguous()
+    elif B is None:
+        raise ValueError("encode needs info or B")
+    device = torch.device(device if device is not None else "cuda")
+    if device.type != "cuda":
+        raise RuntimeError("encode runs on the ROCm device (no CPU path)")
+    if B <= 0:
+        raise ValueError("B must be positive")
+    if out is None:
+        out = torch.empty((B, L), dtype=torch.uint8, device=device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, L) or not out.is_contiguous() or out.device.type != "cuda":
+        raise ValueError(f"out must be a contiguous uint8 [{B}, {L}] device tensor")
+    if ib is not None and ib.device != out.device:
+        raise ValueError(f"info is on {ib.device}, out on {out.device}")
+    _lib.check(_lib.lib().nldpc_encode(graph.handle(out.device), _lib.ptr(ib), B, int(seed) & (2 ** 64 - 1), int(b_offset),
+                                       out.data_ptr(), _lib.stream_of(out.device)), "nldpc_encode")
     return out
 
 

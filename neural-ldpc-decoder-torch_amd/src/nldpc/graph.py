@@ -62,6 +62,34 @@ class LiftedGraph:
                 self._handles[idx] = h
         return h
 
+    # ------------------------------------------------------------------ systematic encoder
+    @property
+    def K(self) -> int:
+        """Info columns of the base graph: the first N - M (the last M are parity columns)."""
+        return self.N - self.M
+
+    def encode_plan(self) -> dict:
+        """The systematic encoder's substitution order (nldpc_encode_plan; host only, no GPU) as int32 numpy arrays:
+        step_col / step_shift / step_level [M], step_ptr [M+1], term_col / term_shift [n_terms], and n_levels.
+        Step s sets y[step_col[s]][(h + step_shift[s]) % Z] to the XOR over k in step_ptr[s]..step_ptr[s+1] of
+        y[term_col[k]][(h + term_shift[k]) % Z] for every h; steps are sorted by level, and a term column is an info
+        column or the target of a step of a lower level.  Raises NldpcUnsupported when the parity part of the base
+        graph cannot be solved by substitution."""
+        cap = 2 * self.E
+        i32 = lambda n: np.zeros(n, dtype=np.int32)  # noqa: E731
+        out = dict(step_col=i32(self.M), step_shift=i32(self.M), step_level=i32(self.M), step_ptr=i32(self.M + 1),
+                   term_col=i32(cap), term_shift=i32(cap))
+        tbl = np.ascontiguousarray(self.basegraph, dtype=np.int32)
+        p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))  # noqa: E731
+        nlev = ctypes.c_int32()
+        _lib.check(_lib.lib().nldpc_encode_plan(self.M, self.N, self.Z, p(tbl), p(out["step_col"]), p(out["step_shift"]),
+                                                p(out["step_level"]), p(out["step_ptr"]), p(out["term_col"]),
+                                                p(out["term_shift"]), cap, ctypes.byref(nlev)), "nldpc_encode_plan")
+        n = int(out["step_ptr"][-1])
+        out["term_col"], out["term_shift"] = out["term_col"][:n].copy(), out["term_shift"][:n].copy()
+        out["n_levels"] = int(nlev.value)
+        return out
+
     def index_tensor(self, name: str, device) -> torch.Tensor:
         """int64 index tables on a device (chk / var) for differentiable weight expansion."""
         key = (name, str(device))
