@@ -295,6 +295,46 @@ int nldpc_encode_plan(int32_t M, int32_t N, int32_t Z, const int32_t* basegraph,
 int nldpc_encode(const nldpc_graph* g, const uint8_t* info, int64_t B, uint64_t seed, int64_t b_offset, uint8_t* y,
                  void* stream);
 
+/* ---- circular-buffer rate matching and LLR rate recovery (additive to ABI 4): implements the bit selection and bit
+ *      interleaving of 3GPP TS 38.212 §5.4.2 (filler skipping, redundancy-version start, limited buffer), generalised
+ *      to graphs without 5G's two punctured columns.  The reference has no counterpart: it runs a graph at its mother
+ *      rate, apart from one Puncture(start, end) range (nldpc_channel_llr).
+ *   With K = N - M, P = punct_cols * Z, codeword y[0 .. N*Z): the buffer is d[p] = y[P + p], p in [0, Ncb), Ncb = ncb or
+ *      N*Z - P when ncb == 0; the last F = n_filler info bits (buffer positions [f0, f1) = [K*Z - F - P, K*Z - P)) are
+ *      known zeros and never sent.  Selection (§5.4.2.1): k = j = 0; while k < E: p = (k0 + j) mod Ncb; if p is not a
+ *      filler, e[k++] = d[p]; j++.  Interleaver (§5.4.2.2): f[i + j*qm] = e[i*(E/qm) + j], i < qm, j < E/qm.
+ *   Rules (NLDPC_EINVAL otherwise): 0 <= punct_cols <= K; 0 <= F <= (K - punct_cols)*Z; ncb == 0 or
+ *      K*Z - P <= ncb <= N*Z - P; Ncb - F >= 1; 0 <= k0 < Ncb; E >= 1, qm >= 1, E % qm == 0; E < 2^31, N*Z < 2^31.
+ *   nldpc_rm_k0 (host only): Table 5.4.2.1-2, k0 = floor(num * ncb / (den * Z)) * Z with num / den for rv 0..3 =
+ *      {0, 17, 33, 56} / 66 (bg 1), {0, 13, 25, 43} / 50 (bg 2); ncb > 0 (the resolved buffer length).
+ *   nldpc_rm_index (host only, no device, no graph handle): idx[m], m in [0, E), = the codeword bit index f[m]
+ *      carries, computed with the inline functions the kernels use (csrc/nldpc_rm_index.h).
+ *   nldpc_rate_match: y [B][N*Z] uint8 (any non-zero byte is 1) -> f [B][E] uint8 0/1, f[b][m] = y[b][idx[m]].
+ *   nldpc_rate_recover: llr [B][E] fp32 in the order of f -> xa [B][N][Z] fp32 (the decoder's input).  Per codeword
+ *      position n: a filler position is set to filler_value (the shortening convention: -|llr_hi|); a position that
+ *      idx names at least once gets acc = (accumulate ? xa[n] : +0) plus its received values added one by one in
+ *      ascending selection index k (one fp32 rounding each), clamped to [-clip, clip] when clip > 0 (a NaN stays a
+ *      NaN); every other position (n < P, beyond the buffer, never selected) is set to erasure_value when
+ *      accumulate == 0 and left unwritten when accumulate == 1.  A further redundancy version is soft-combined by
+ *      calling again with accumulate = 1 on the same xa.  The Neural check node masks exact zeros out of its minimum
+ *      (NeuralLDPCDecoder.py:74-75), so an erasure_value of 0 is not an erasure for it: use a small non-zero value.
+ *   Both launches are stream-ordered, synchronise and allocate nothing, write nothing outside f / xa, and work for
+ *      any graph and Z (only the graph's dimensions are read; no fused kernel, no device table). */
+typedef struct nldpc_rm {
+    int32_t punct_cols;  /* leading base columns never sent (5G: 2; otherwise 0) */
+    int32_t qm;          /* interleaver rows; 1 = none; divides E */
+    int64_t n_filler;    /* F */
+    int64_t ncb;         /* 0 = the full buffer N*Z - P */
+    int64_t k0;          /* start position in the buffer */
+    int64_t E;           /* bits sent per codeword */
+} nldpc_rm;
+int nldpc_rm_k0(int32_t bg, int32_t rv, int64_t ncb, int32_t Z, int64_t* k0);
+int nldpc_rm_index(int32_t M, int32_t N, int32_t Z, const nldpc_rm* rm, int32_t* idx);
+int nldpc_rate_match(const nldpc_graph* g, const nldpc_rm* rm, const uint8_t* y, int64_t B, uint8_t* f,
+                     void* stream);
+int nldpc_rate_recover(const nldpc_graph* g, const nldpc_rm* rm, const float* llr, int64_t B, float erasure_value,
+                       float filler_value, float clip, int32_t accumulate, float* xa, void* stream);
+
 /* ---- benchmark instrumentation: per-kernel HIP-event timing of nldpc_forward / nldpc_backward
  *   launches.  nldpc_profile_begin arms a recorder for up to `capacity` launches (not thread-safe);
  *   nldpc_profile_end synchronises on the recorded events and returns summed milliseconds and

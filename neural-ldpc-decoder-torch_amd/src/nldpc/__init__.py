@@ -5,6 +5,7 @@ Layers:
   nldpc.graph       lifted QC graph as an edge list, device handles
   nldpc.decode      decode / autograd over nldpc_forward / nldpc_backward
   nldpc.channel     on-device AWGN channel and fused BER/FER counters
+  nldpc.ratematch   circular-buffer rate matching and LLR rate recovery (TS 38.212 §5.4.2) around the channel
   nldpc.distributed one-process-per-GPU sharded decoding with an RCCL reduction of the counters
 The drop-in packages neural_ldpc_decoder, boosted_neural_ldpc_decoder and checkpoint_utils (next to
 this package) mirror the reference's Python API on top of it.

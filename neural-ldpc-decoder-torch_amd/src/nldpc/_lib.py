@@ -30,12 +30,14 @@ EXPORTED = (
     "nldpc_awgn_llr", "nldpc_profile_begin", "nldpc_profile_end", "nldpc_bce_workspace", "nldpc_bce_loss",
     "nldpc_bce_grad", "nldpc_bce_loss_grad", "nldpc_bce_grad_unless_unit", "nldpc_forward_count", "nldpc_channel_llr", "nldpc_hbm_probe",
     "nldpc_code_object_sig", "nldpc_syndrome", "nldpc_forward_early_stop", "nldpc_encode_plan", "nldpc_encode",
+    "nldpc_rm_k0", "nldpc_rm_index", "nldpc_rate_match", "nldpc_rate_recover",
 )
 
 
 # entries added after the ABI 4 structs were fixed (no layout change): optional in older builds
 _ADDED_IN_ABI4 = ("nldpc_bce_loss_grad", "nldpc_bce_grad_unless_unit", "nldpc_code_object_sig", "nldpc_syndrome",
-                  "nldpc_forward_early_stop", "nldpc_encode_plan", "nldpc_encode")
+                  "nldpc_forward_early_stop", "nldpc_encode_plan", "nldpc_encode", "nldpc_rm_k0", "nldpc_rm_index",
+                  "nldpc_rate_match", "nldpc_rate_recover")
 
 
 class NldpcCfg(ctypes.Structure):
@@ -50,6 +52,17 @@ class NldpcCfg(ctypes.Structure):
         ("c2v_in", ctypes.c_int32),
         ("vn_prefix", ctypes.c_int32),
         ("flags", ctypes.c_int32),
+    ]
+
+
+class NldpcRm(ctypes.Structure):
+    _fields_ = [
+        ("punct_cols", ctypes.c_int32),
+        ("qm", ctypes.c_int32),
+        ("n_filler", ctypes.c_int64),
+        ("ncb", ctypes.c_int64),
+        ("k0", ctypes.c_int64),
+        ("E", ctypes.c_int64),
     ]
 
 
@@ -97,6 +110,11 @@ def _declare(lib):
                                             _vp, _vp]),
         "nldpc_encode_plan": (_i32, [_i32, _i32, _i32] + [ctypes.POINTER(_i32)] * 7 + [_i32, ctypes.POINTER(_i32)]),
         "nldpc_encode": (_i32, [_vp, _vp, _i64, ctypes.c_uint64, _i64, _vp, _vp]),
+        "nldpc_rm_k0": (_i32, [_i32, _i32, _i64, _i32, ctypes.POINTER(_i64)]),
+        "nldpc_rm_index": (_i32, [_i32, _i32, _i32, ctypes.POINTER(NldpcRm), ctypes.POINTER(_i32)]),
+        "nldpc_rate_match": (_i32, [_vp, ctypes.POINTER(NldpcRm), _vp, _i64, _vp, _vp]),
+        "nldpc_rate_recover": (_i32, [_vp, ctypes.POINTER(NldpcRm), _vp, _i64, ctypes.c_float, ctypes.c_float,
+                                      ctypes.c_float, _i32, _vp, _vp]),
         "nldpc_awgn_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp]),
         "nldpc_channel_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp, _i64, _i64,
                                      ctypes.c_float, _i64, _i64, ctypes.c_float, _vp]),

@@ -35,7 +35,9 @@ def awgn_llr(B: int, N: int, Z: int, sigma: float, *, seed: int = 2042, b_offset
     """[B, N, Z] fp32 channel LLRs on the device.  y: [B, N*Z] codeword bits (None = all-zero);
     puncturing / shortening: (start, end) 1-based inclusive bit ranges of every codeword, or objects
     with .start / .end (the reference's Puncture / Shortening; start 0 = none), set after the QMS
-    quantiser to puncture_value (reference: 0, 0.001 for SP) / shortening_value (-|llr_hi|)."""
+    quantiser to puncture_value (reference: 0, 0.001 for SP) / shortening_value (-|llr_hi|).  For the Neural decoder
+    an exact 0 is not an erasure (its check node masks zeros out of the minimum): punctured or rate-matched
+    (nldpc.ratematch) Neural decoding of real codewords needs a small non-zero value such as 0.001."""
     device = torch.device(device if device is not None else "cuda")
     if out is None:
         out = torch.empty((B, N, Z), dtype=torch.float32, device=device)
