@@ -335,6 +335,51 @@ int nldpc_rate_match(const nldpc_graph* g, const nldpc_rm* rm, const uint8_t* y,
 int nldpc_rate_recover(const nldpc_graph* g, const nldpc_rm* rm, const float* llr, int64_t B, float erasure_value,
                        float filler_value, float clip, int32_t accumulate, float* xa, void* stream);
 
+/* ---- QAM modulation and soft demapping (additive to ABI 4): the channel between nldpc_rate_match and
+ *      nldpc_rate_recover for the modulations NR uses with LDPC (3GPP TS 38.211 §5.1.3-5.1.6: QPSK, 16-, 64-, 256-QAM);
+ *      nldpc_channel_llr stays the BPSK channel (qm = 1).  The reference has no counterpart (BPSK only,
+ *      AWGNPassedDatagen.py:97-103).  The arithmetic is the inline functions of csrc/nldpc_qam.h on host and device.
+ *   qm in {2, 4, 6, 8}, h = qm / 2.  A symbol carries qm consecutive bits b_0 .. b_{qm-1} of f, f[b][s*qm + i] -- the
+ *      grouping nldpc_rate_match's interleaver produces with the same qm --; its I dimension takes c_k = b_{2k}, its Q
+ *      dimension c_k = b_{2k+1}, k < h.  Integer amplitude a = (1-2c_0)[2^{h-1} - (1-2c_1)[2^{h-2} - .. - (1-2c_{h-1})]]
+ *      (odd, |a| <= 2^h - 1); level = (float)a * A, one fp32 rounding, A = the fp32 nearest to 1/sqrt(2), 1/sqrt(10),
+ *      1/sqrt(42), 1/sqrt(170) (unit average symbol energy).  Symbols are interleaved fp32 pairs (I, Q), S = E / qm
+ *      per codeword.
+ *   LLR = log P(b=1)/P(b=0): LLR > 0 means bit 1 (nldpc_ber_count convention 0, the decoders).  38.211 keeps bit 0 on
+ *      the positive side, so a noiseless symbol gives negative LLRs for its 0 bits.
+ *   Demapper, per real dimension with received x: for each of the 2^h levels l, t = x - l and d = t * t (two fp32
+ *      roundings, no FMA); w = (float)(1.0 / (2.0 * (double)sigma * (double)sigma)); sigma is the noise standard
+ *      deviation per real dimension.
+ *        method 0 (max-log): LLR_k = (min_{c_k=0} d - min_{c_k=1} d) * w
+ *        method 1 (log-MAP): with m = -(d * w), lse_v = M_v + logf(sum_{c_k=v} expf(m - M_v)), M_v = max_{c_k=v} m, the
+ *                            sum in ascending order of the label c_0 .. c_{h-1} read as a binary number, from +0;
+ *                            LLR_k = lse_1 - lse_0 (fp32 throughout)
+ *   nldpc_qam_points (host only): iq[2v], iq[2v+1] = (I, Q) of the symbol of bits b_i = (v >> (qm-1-i)) & 1, v < 2^qm.
+ *   nldpc_qam_demap_ref (host only, no device): sym host [S][2] -> llr host [S*qm], the functions the kernels run.
+ *   nldpc_qam_modulate: f [B][E] uint8 (any non-zero byte is 1) -> sym [B][S][2].
+ *   nldpc_qam_demap: sym [B][S][2] -> llr [B][S*qm] in the order of f.
+ *   nldpc_qam_channel_llr: bits -> symbols -> AWGN -> LLRs in one kernel (no symbol goes through memory).  f NULL = the
+ *      all-zero word.  Noisy symbol r = (float)((double)level + (double)sigma * n), one rounding per dimension; llr is
+ *      bit for bit what nldpc_qam_demap computes from those r; sym_out (nullable) receives the r, [B][S][2].  n: with
+ *      G = (b_offset + b) * S + s the global index of a symbol, the four fp64 Box-Muller normals of nldpc_channel_llr
+ *      (sqrt(-2 ln u0) cos(2 pi u1), .. sin .., the same of (u2, u3); u = (word + 1) / 2^32) of Philox-4x32-10 at
+ *      counter (lo32(G >> 1), hi32(G >> 1), 0x51414D31, 0), key (lo32(seed), hi32(seed)), are (I, Q) of the even symbol
+ *      2 (G >> 1), then (I, Q) of the odd one.  Counter word 2 ("QAM1") keeps the stream apart from the BPSK noise (0)
+ *      and the encoder's info bits (0x454E4331); a shard that starts at b_offset draws the unsharded batch's noise,
+ *      also when S and b_offset are odd and a pair straddles two codewords.
+ *   NLDPC_EINVAL: qm not in {2, 4, 6, 8}, method not 0 / 1, E % qm != 0, !(sigma > 0), B <= 0, E <= 0 (S <= 0),
+ *      E >= 2^31 (S * qm >= 2^31), b_offset < 0, a NULL required pointer, a float pointer off a 4-byte boundary (f may
+ *      start anywhere).  NLDPC_EUNSUPPORTED: B or b_offset >= 2^31.
+ *   The three launches are stream-ordered on the current device, synchronise and allocate nothing and write nothing
+ *      outside sym / llr / sym_out. */
+int nldpc_qam_points(int32_t qm, float* iq);
+int nldpc_qam_demap_ref(int32_t qm, int32_t method, float sigma, const float* sym, int64_t S, float* llr);
+int nldpc_qam_modulate(int32_t qm, const uint8_t* f, int64_t B, int64_t E, float* sym, void* stream);
+int nldpc_qam_demap(int32_t qm, int32_t method, float sigma, const float* sym, int64_t B, int64_t S, float* llr,
+                    void* stream);
+int nldpc_qam_channel_llr(int32_t qm, int32_t method, const uint8_t* f, int64_t B, int64_t E, float sigma,
+                          uint64_t seed, int64_t b_offset, float* llr, float* sym_out, void* stream);
+
 /* ---- benchmark instrumentation: per-kernel HIP-event timing of nldpc_forward / nldpc_backward
  *   launches.  nldpc_profile_begin arms a recorder for up to `capacity` launches (not thread-safe);
  *   nldpc_profile_end synchronises on the recorded events and returns summed milliseconds and

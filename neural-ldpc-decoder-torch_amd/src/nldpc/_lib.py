@@ -31,13 +31,15 @@ EXPORTED = (
     "nldpc_bce_grad", "nldpc_bce_loss_grad", "nldpc_bce_grad_unless_unit", "nldpc_forward_count", "nldpc_channel_llr", "nldpc_hbm_probe",
     "nldpc_code_object_sig", "nldpc_syndrome", "nldpc_forward_early_stop", "nldpc_encode_plan", "nldpc_encode",
     "nldpc_rm_k0", "nldpc_rm_index", "nldpc_rate_match", "nldpc_rate_recover",
+    "nldpc_qam_points", "nldpc_qam_demap_ref", "nldpc_qam_modulate", "nldpc_qam_demap", "nldpc_qam_channel_llr",
 )
 
 
 # entries added after the ABI 4 structs were fixed (no layout change): optional in older builds
 _ADDED_IN_ABI4 = ("nldpc_bce_loss_grad", "nldpc_bce_grad_unless_unit", "nldpc_code_object_sig", "nldpc_syndrome",
                   "nldpc_forward_early_stop", "nldpc_encode_plan", "nldpc_encode", "nldpc_rm_k0", "nldpc_rm_index",
-                  "nldpc_rate_match", "nldpc_rate_recover")
+                  "nldpc_rate_match", "nldpc_rate_recover", "nldpc_qam_points", "nldpc_qam_demap_ref",
+                  "nldpc_qam_modulate", "nldpc_qam_demap", "nldpc_qam_channel_llr")
 
 
 class NldpcCfg(ctypes.Structure):
@@ -115,6 +117,13 @@ def _declare(lib):
         "nldpc_rate_match": (_i32, [_vp, ctypes.POINTER(NldpcRm), _vp, _i64, _vp, _vp]),
         "nldpc_rate_recover": (_i32, [_vp, ctypes.POINTER(NldpcRm), _vp, _i64, ctypes.c_float, ctypes.c_float,
                                       ctypes.c_float, _i32, _vp, _vp]),
+        "nldpc_qam_points": (_i32, [_i32, ctypes.POINTER(ctypes.c_float)]),
+        "nldpc_qam_demap_ref": (_i32, [_i32, _i32, ctypes.c_float, ctypes.POINTER(ctypes.c_float), _i64,
+                                       ctypes.POINTER(ctypes.c_float)]),
+        "nldpc_qam_modulate": (_i32, [_i32, _vp, _i64, _i64, _vp, _vp]),
+        "nldpc_qam_demap": (_i32, [_i32, _i32, ctypes.c_float, _vp, _i64, _i64, _vp, _vp]),
+        "nldpc_qam_channel_llr": (_i32, [_i32, _i32, _vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _vp, _vp,
+                                         _vp]),
         "nldpc_awgn_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp]),
         "nldpc_channel_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp, _i64, _i64,
                                      ctypes.c_float, _i64, _i64, ctypes.c_float, _vp]),

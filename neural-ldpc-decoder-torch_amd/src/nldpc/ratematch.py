@@ -8,7 +8,9 @@ rate_match     codewords [B, N*Z] -> sent bits [B, E] (nldpc_rate_match).
 rate_recover   received LLRs [B, E] -> decoder input [B, N, Z], repetitions and further redundancy versions
                soft-combined (nldpc_rate_recover).
 
-The channel between the two is channel.awgn_llr(B, E, 1, sigma, y=f).reshape(B, E).
+The channel between the two is channel.awgn_llr(B, E, 1, sigma, y=f).reshape(B, E) for BPSK (qm = 1), or
+modulation.qam_llr(f, qm, sigma) for 2^qm-QAM with qm = 2, 4, 6, 8: a symbol takes qm consecutive bits of f, the
+groups the interleaver forms with RateMatch(qm=qm).
 
 Unsent positions get `erasure_value`.  An exact 0 is NOT an erasure for the Neural decoder: the reference's check node
 masks zeros out of its minimum (NeuralLDPCDecoder.py:74-75), so an unsent degree-1 extension column drops out of its
