@@ -380,6 +380,50 @@ int nldpc_qam_demap(int32_t qm, int32_t method, float sigma, const float* sym, i
 int nldpc_qam_channel_llr(int32_t qm, int32_t method, const uint8_t* f, int64_t B, int64_t E, float sigma,
                           uint64_t seed, int64_t b_offset, float* llr, float* sym_out, void* stream);
 
+/* ---- CRC attachment and checking (additive to ABI 4): the cyclic redundancy checks of 3GPP TS 38.212 §5.1, the step in
+ *      front of nldpc_encode and behind the decoder.  The reference has no counterpart (its error figures all need the
+ *      transmitted word).  The arithmetic is the inline functions of csrc/nldpc_crc.h on host and device.
+ *   Polynomials: enum nldpc_crc, lengths L = 24, 24, 24, 16, 11, 6; without the leading term x^L they are 0x864CFB,
+ *      0x800063, 0xB2B117, 0x1021, 0x621, 0x21.
+ *   Rule: bits a_0 .. a_{A-1} get parity p_0 .. p_{L-1} so that a_0 x^{A+L-1} + .. + a_{A-1} x^L + p_0 x^{L-1} + .. +
+ *      p_{L-1} is divisible by g(x) over GF(2).  The register starts at zero, nothing is reflected and there is no
+ *      final XOR.  A block passes when the remainder of its first A + L bits is zero.  Two consequences: leading zero
+ *      bits do not change the remainder (a payload may be padded in front for free), and the all-zero block passes (an
+ *      all-zero posterior, e.g. of a dead input, is not flagged; nldpc_syndrome does not flag it either).  A CRC pass and
+ *      syndrome weight 0 are different verdicts: a wrong codeword has syndrome 0 and, but for a chance of 2^-L, fails
+ *      its CRC.
+ *   nldpc_crc_ref (host only, no device): *parity = the L parity bits of bits[0..A) (any non-zero byte is 1), p_0 the
+ *      most significant of the low L bits.  Computed with the functions the kernels use: the remainder of each
+ *      chunk-bit piece (the last may be shorter), multiplied by x^n mod g for the n bits that follow it, XORed
+ *      together; chunk >= 1 is the caller's, every value gives the same result.
+ *   nldpc_crc_attach: a [B][A] uint8 (any non-zero byte is 1), or NULL -> info [B][W] uint8, written in full: [0, A) the
+ *      payload as 0 / 1, [A, A+L) the parity, p_0 first, [A+L, W) zeros (filler bits).  With W = K*Z this is
+ *      nldpc_encode's info, and nldpc_rm.n_filler = W - A - L.  a == NULL: the payload is drawn on the device from the
+ *      encoder's info-bit stream: bit i < A of block c = b_offset + b is the bit nldpc_encode(info = NULL) documents
+ *      for a row of K*Z = W bits (counter word 2 = 0x454E4331, W' = ceil(W / 128) counters per block), so the first A
+ *      bits equal those of nldpc_encode with the same seed and a sharded batch draws the unsharded one's payloads.
+ *      NLDPC_EINVAL unless B >= 1, A >= 1, A + L <= W < 2^31, b_offset >= 0, info non-NULL; NLDPC_EUNSUPPORTED for B or
+ *      b_offset >= 2^31.
+ *   nldpc_crc_check: exactly one of llr (fp32 [B][stride]; hard decision by `convention` as nldpc_ber_count, so an
+ *      exact 0, -0 or NaN is bit 0 under convention 0) and bits (uint8 [B][stride], non-zero is 1) is given; the first
+ *      A + L positions of each row are checked.  stride >= A + L is in elements and need not be a multiple of anything:
+ *      a decoder posterior [B][N*Z] is passed as it is (its first K*Z positions are the info bits).  ok: uint8 [B],
+ *      nullable, 1 when the block passes, else 0.  ref: nullable, the true bits [B][ref_stride] (e.g. nldpc_encode's y
+ *      with ref_stride = N*Z, >= A + L).  counts: nullable device int64[3], += as nldpc_ber_count does: [0] blocks whose
+ *      CRC fails; [1] blocks whose CRC passes although their A + L bits differ from ref (undetected errors); [2] blocks
+ *      whose A + L bits differ from ref; [1] and [2] get nothing without ref.  At least one of ok and counts is non-NULL.
+ *      NLDPC_EINVAL: B < 1, A < 1, A + L >= 2^31, a stride below A + L, convention not 0 / 1, both or neither of llr and
+ *      bits, ok and counts both NULL, llr off a 4-byte or counts off an 8-byte boundary; NLDPC_EUNSUPPORTED: B >= 2^31.
+ *   Both launches are stream-ordered on the current device, synchronise and allocate nothing, write nothing outside
+ *      info / ok / counts and need no graph handle. */
+enum nldpc_crc { NLDPC_CRC24A = 0, NLDPC_CRC24B, NLDPC_CRC24C, NLDPC_CRC16, NLDPC_CRC11, NLDPC_CRC6 };
+int nldpc_crc_ref(int32_t crc, const uint8_t* bits, int64_t A, int64_t chunk, uint32_t* parity);
+int nldpc_crc_attach(int32_t crc, const uint8_t* a, int64_t B, int64_t A, int64_t W, uint64_t seed, int64_t b_offset,
+                     uint8_t* info, void* stream);
+int nldpc_crc_check(int32_t crc, const float* llr, const uint8_t* bits, int64_t B, int64_t A, int64_t stride,
+                    int32_t convention, const uint8_t* ref, int64_t ref_stride, uint8_t* ok, int64_t* counts,
+                    void* stream);
+
 /* ---- benchmark instrumentation: per-kernel HIP-event timing of nldpc_forward / nldpc_backward
  *   launches.  nldpc_profile_begin arms a recorder for up to `capacity` launches (not thread-safe);
  *   nldpc_profile_end synchronises on the recorded events and returns summed milliseconds and

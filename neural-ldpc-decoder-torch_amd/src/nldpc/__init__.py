@@ -7,6 +7,8 @@ Layers:
   nldpc.channel     on-device AWGN channel and fused BER/FER counters
   nldpc.ratematch   circular-buffer rate matching and LLR rate recovery (TS 38.212 §5.4.2) around the channel
   nldpc.modulation  QAM modulation, soft demapping and the fused QAM/AWGN channel (TS 38.211 §5.1.3-5.1.6)
+  nldpc.crc         CRC attachment in front of the encoder, CRC checking and error accounting behind the decoder
+                    (TS 38.212 §5.1)
   nldpc.distributed one-process-per-GPU sharded decoding with an RCCL reduction of the counters
 The drop-in packages neural_ldpc_decoder, boosted_neural_ldpc_decoder and checkpoint_utils (next to
 this package) mirror the reference's Python API on top of it.

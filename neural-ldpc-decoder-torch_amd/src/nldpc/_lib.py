@@ -32,6 +32,7 @@ EXPORTED = (
     "nldpc_code_object_sig", "nldpc_syndrome", "nldpc_forward_early_stop", "nldpc_encode_plan", "nldpc_encode",
     "nldpc_rm_k0", "nldpc_rm_index", "nldpc_rate_match", "nldpc_rate_recover",
     "nldpc_qam_points", "nldpc_qam_demap_ref", "nldpc_qam_modulate", "nldpc_qam_demap", "nldpc_qam_channel_llr",
+    "nldpc_crc_ref", "nldpc_crc_attach", "nldpc_crc_check",
 )
 
 
@@ -39,7 +40,8 @@ EXPORTED = (
 _ADDED_IN_ABI4 = ("nldpc_bce_loss_grad", "nldpc_bce_grad_unless_unit", "nldpc_code_object_sig", "nldpc_syndrome",
                   "nldpc_forward_early_stop", "nldpc_encode_plan", "nldpc_encode", "nldpc_rm_k0", "nldpc_rm_index",
                   "nldpc_rate_match", "nldpc_rate_recover", "nldpc_qam_points", "nldpc_qam_demap_ref",
-                  "nldpc_qam_modulate", "nldpc_qam_demap", "nldpc_qam_channel_llr")
+                  "nldpc_qam_modulate", "nldpc_qam_demap", "nldpc_qam_channel_llr", "nldpc_crc_ref", "nldpc_crc_attach",
+                  "nldpc_crc_check")
 
 
 class NldpcCfg(ctypes.Structure):
@@ -124,6 +126,9 @@ def _declare(lib):
         "nldpc_qam_demap": (_i32, [_i32, _i32, ctypes.c_float, _vp, _i64, _i64, _vp, _vp]),
         "nldpc_qam_channel_llr": (_i32, [_i32, _i32, _vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _vp, _vp,
                                          _vp]),
+        "nldpc_crc_ref": (_i32, [_i32, _vp, _i64, _i64, ctypes.POINTER(ctypes.c_uint32)]),
+        "nldpc_crc_attach": (_i32, [_i32, _vp, _i64, _i64, _i64, ctypes.c_uint64, _i64, _vp, _vp]),
+        "nldpc_crc_check": (_i32, [_i32, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp]),
         "nldpc_awgn_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp]),
         "nldpc_channel_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp, _i64, _i64,
                                      ctypes.c_float, _i64, _i64, ctypes.c_float, _vp]),
