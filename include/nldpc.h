@@ -424,6 +424,84 @@ int nldpc_crc_check(int32_t crc, const float* llr, const uint8_t* bits, int64_t 
                     int32_t convention, const uint8_t* ref, int64_t ref_stride, uint8_t* ok, int64_t* counts,
                     void* stream);
 
+/* ---- transport blocks (additive to ABI 4): code-block segmentation with the code-block CRC (3GPP TS 38.212 §5.2.2),
+ *      the per-block rate-matching lengths E_r (§5.4.2.1), code-block concatenation (§5.5) and, at the receiver, the
+ *      inverses and the transport-block verdict.  The reference has no counterpart.  The arithmetic is the inline
+ *      functions of csrc/nldpc_tb.h and csrc/nldpc_crc.h on host and device.
+ *   Sizes: a payload of A bits carries a TB CRC (tb_crc, one of enum nldpc_crc; §5.1 uses CRC24A, or CRC16 up to A = 3824)
+ *      of L_tb bits: B' = A + L_tb.  The TB is cut into C parts of K' - L bits, B' = C (K' - L); a part followed by its
+ *      CRC24B of L bits (L = 24, or 0 when C == 1: no code-block CRC) and F = W - K' filler zeros is one code block, a row
+ *      of W bits (nldpc_encode's info with W = K*Z; nldpc_rm.n_filler = F).
+ *   Layout: a batch of Btb transport blocks is BLOCK-MAJOR: code block r of TB t is row r * Btb + t of every
+ *      per-code-block array, so the blocks that share a rate-matching length are one contiguous range of rows and
+ *      nldpc_encode, nldpc_rate_match, nldpc_rate_recover, the decoders and nldpc_crc_check run on it unchanged.
+ *   nldpc_tb_plan (host only): B' = A + L_tb; kcb == 0 means W; B' <= kcb: C = 1, L = 0; otherwise L = 24 and
+ *      C = ceil(B' / (kcb - 24)); B'' = B' + C L, K' = B'' / C, F = W - K'.  NLDPC_EINVAL: tb_crc not of enum nldpc_crc,
+ *      A < 1, W < 1, kcb < 0, kcb > W, kcb <= 24 when B' > kcb, C does not divide B'', K' > W, or A, W, kcb, B' or
+ *      B'' >= 2^31.  The launches below take any plan that satisfies these relations (C need not be the smallest).
+ *   nldpc_tb_lifting_size (host only, a helper: the plan takes whatever graph the caller has): Bp = B'.  Kb of §5.2.2
+ *      (bg 1: 22; bg 2: 10 / 9 / 8 / 6 for B' > 640 / > 560 / > 192 / else) and Zc, the smallest Z = a * 2^j <= 384,
+ *      a in {2, 3, 5, 7, 9, 11, 13, 15} (Table 5.3.2-1), with Kb * Z >= K', K' = ceil(B'' / C) for the base graph's own
+ *      Kcb (8448 / 3840).  NLDPC_EINVAL: bg not 1 / 2, Bp < 1 or >= 2^31, a NULL pointer, no size large enough.
+ *   nldpc_tb_er (host only): with G' = G / (NL Qm), blocks r < C_lo = C - (G' mod C) get E_lo = NL Qm floor(G' / C), the
+ *      others E_hi = NL Qm ceil(G' / C) (E_hi == E_lo when C divides G').  NLDPC_EINVAL unless NL, Qm, C >= 1,
+ *      1 <= G < 2^31, NL Qm divides G and E_lo >= 1.
+ *   nldpc_tb_crc_ref (host only, no device): one TB as its C host rows blocks[r * stride ..], uint8 (any non-zero byte is
+ *      1), stride >= K'.  cb_ok[r] (nullable, [C]) = 1 when the first K' bits of row r pass CRC24B (C == 1: when the TB
+ *      CRC passes).  *tb_rem (nullable) = what nldpc_crc_ref(tb_crc) gives as the parity of the reassembled B' bits
+ *      (TB(x) x^L_tb mod g), 0 = the TB passes: the remainder of each part under the TB polynomial, combined by
+ *      acc = acc * x^{K' - L} xor R(part r) over r = 0 .. C-1 with the functions nldpc_tb_check runs.
+ *   nldpc_tb_segment: tb uint8 [Btb][B'] (the TB bits with the TB CRC, what nldpc_crc_attach writes with W = B'; any
+ *      non-zero byte is 1) -> info uint8 [C * Btb][W], written in full: row r * Btb + t = tb[t][r (K'-L) .. (r+1)(K'-L))
+ *      as 0 / 1, the CRC24B parity of those bits, p_0 first (nothing when C == 1), F zeros.
+ *   nldpc_tb_concat: elem_bytes 1 (bits) or 4 (fp32 / any 4-byte element, copied as it is).  f_lo [C_lo * Btb][E_lo]
+ *      and f_hi [(C - C_lo) * Btb][E_hi], block-major (f_lo NULL allowed when C_lo == 0 -- never produced by
+ *      nldpc_tb_er --, f_hi when C_lo == C) -> g [Btb][G], G = C_lo E_lo + (C - C_lo) E_hi: block r of TB t sits at
+ *      g[t][sum_{j<r} E_j ..].  nldpc_tb_deconcat is the inverse, g -> f_lo, f_hi.  Elements are copied unchanged.
+ *      NLDPC_EINVAL: elem_bytes not 1 / 4, Btb < 1, C < 1, C_lo outside [0, C], E_lo or E_hi < 1, G or C * Btb >= 2^31,
+ *      a NULL pointer that is needed, a pointer off a 4-byte boundary when elem_bytes == 4.
+ *   nldpc_tb_check: exactly one of llr (fp32 [C * Btb][stride], hard decision by `convention` as nldpc_crc_check) and
+ *      bits (uint8 [C * Btb][stride], non-zero is 1); stride >= K' in elements: decoder posteriors [C * Btb][N*Z] go in as
+ *      they are.  The first K' positions of every row are read once.  cb_ok uint8 [C * Btb] (nullable): 1 when the
+ *      block's CRC24B passes (C == 1: the TB verdict).  tb_ok uint8 [Btb] (nullable): 1 when the TB CRC over the
+ *      reassembled B' bits passes; it is combined from the per-part remainders, no TB is materialised for it.  tb_out
+ *      uint8 [Btb][B'] (nullable): the reassembled bits as 0 / 1 (desegmentation).  ref_tb uint8 [Btb][B'] (nullable,
+ *      non-zero is 1): the true TB bits.  counts (nullable) device int64[4], +=: [0] TBs whose TB CRC fails; [1] TBs that
+ *      pass although their B' bits differ from ref_tb (undetected errors); [2] TBs whose B' bits differ from ref_tb;
+ *      [3] code blocks whose CRC fails (C == 1: equal to [0]); [1] and [2] get nothing without ref_tb.  The all-zero TB
+ *      passes, and a TB in which a code block was replaced by another valid code block passes every code-block CRC and
+ *      fails only the TB CRC.  work: device scratch of at least the bytes nldpc_tb_workspace answers (4 per code
+ *      block), 4-byte aligned; the first kernel leaves each part's TB remainder there (left-aligned, its error and
+ *      verdict flags in the two lowest bits), a second launch of one thread per TB combines them in ascending r.
+ *      NLDPC_EINVAL: a plan that breaks the relations above, Btb < 1, C * Btb >= 2^31, both or neither of llr and bits,
+ *      stride < K', convention not 0 / 1, every output NULL, work NULL or too small or off a 4-byte boundary, llr off a
+ *      4-byte or counts off an 8-byte boundary.
+ *   All launches are stream-ordered on the current device, synchronise and allocate nothing, write nothing outside
+ *      their outputs (and work) and need no graph handle. */
+typedef struct nldpc_tb {
+    int64_t A;       /* payload bits */
+    int32_t tb_crc;  /* enum nldpc_crc of the TB CRC */
+    int64_t W;       /* bits of a code-block row (K*Z) */
+    int32_t C;       /* code blocks */
+    int32_t L;       /* code-block CRC bits: 24, or 0 when C == 1 */
+    int64_t Kp;      /* K': part + L */
+    int64_t F;       /* filler bits W - K' */
+} nldpc_tb;
+int nldpc_tb_plan(int64_t A, int32_t tb_crc, int64_t W, int64_t kcb, nldpc_tb* plan);
+int nldpc_tb_lifting_size(int32_t bg, int64_t Bp, int32_t* Kb, int32_t* Zc);
+int nldpc_tb_er(int64_t G, int32_t NL, int32_t Qm, int32_t C, int64_t* E_lo, int64_t* E_hi, int32_t* C_lo);
+int nldpc_tb_crc_ref(const nldpc_tb* plan, const uint8_t* blocks, int64_t stride, uint8_t* cb_ok,
+                     uint32_t* tb_rem);
+int nldpc_tb_workspace(const nldpc_tb* plan, int64_t Btb, size_t* bytes);
+int nldpc_tb_segment(const nldpc_tb* plan, const uint8_t* tb, int64_t Btb, uint8_t* info, void* stream);
+int nldpc_tb_concat(int32_t elem_bytes, const void* f_lo, const void* f_hi, int64_t Btb, int32_t C, int32_t C_lo,
+                    int64_t E_lo, int64_t E_hi, void* g, void* stream);
+int nldpc_tb_deconcat(int32_t elem_bytes, const void* g, int64_t Btb, int32_t C, int32_t C_lo, int64_t E_lo,
+                      int64_t E_hi, void* f_lo, void* f_hi, void* stream);
+int nldpc_tb_check(const nldpc_tb* plan, const float* llr, const uint8_t* bits, int64_t Btb, int64_t stride,
+                   int32_t convention, const uint8_t* ref_tb, uint8_t* cb_ok, uint8_t* tb_ok, uint8_t* tb_out,
+                   int64_t* counts, void* work, size_t work_bytes, void* stream);
+
 /* ---- benchmark instrumentation: per-kernel HIP-event timing of nldpc_forward / nldpc_backward
  *   launches.  nldpc_profile_begin arms a recorder for up to `capacity` launches (not thread-safe);
  *   nldpc_profile_end synchronises on the recorded events and returns summed milliseconds and

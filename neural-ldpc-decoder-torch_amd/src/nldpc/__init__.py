@@ -9,6 +9,8 @@ Layers:
   nldpc.modulation  QAM modulation, soft demapping and the fused QAM/AWGN channel (TS 38.211 §5.1.3-5.1.6)
   nldpc.crc         CRC attachment in front of the encoder, CRC checking and error accounting behind the decoder
                     (TS 38.212 §5.1)
+  nldpc.transport   transport blocks: the TB CRC, code-block segmentation, per-block rate matching and concatenation,
+                    and the TB verdict from the per-block remainders (TS 38.212 §5.2.2, §5.4.2.1, §5.5)
   nldpc.distributed one-process-per-GPU sharded decoding with an RCCL reduction of the counters
 The drop-in packages neural_ldpc_decoder, boosted_neural_ldpc_decoder and checkpoint_utils (next to
 this package) mirror the reference's Python API on top of it.

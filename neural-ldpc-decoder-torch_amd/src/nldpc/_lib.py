@@ -33,6 +33,8 @@ EXPORTED = (
     "nldpc_rm_k0", "nldpc_rm_index", "nldpc_rate_match", "nldpc_rate_recover",
     "nldpc_qam_points", "nldpc_qam_demap_ref", "nldpc_qam_modulate", "nldpc_qam_demap", "nldpc_qam_channel_llr",
     "nldpc_crc_ref", "nldpc_crc_attach", "nldpc_crc_check",
+    "nldpc_tb_plan", "nldpc_tb_lifting_size", "nldpc_tb_er", "nldpc_tb_crc_ref", "nldpc_tb_workspace", "nldpc_tb_segment",
+    "nldpc_tb_concat", "nldpc_tb_deconcat", "nldpc_tb_check",
 )
 
 
@@ -41,7 +43,8 @@ _ADDED_IN_ABI4 = ("nldpc_bce_loss_grad", "nldpc_bce_grad_unless_unit", "nldpc_co
                   "nldpc_forward_early_stop", "nldpc_encode_plan", "nldpc_encode", "nldpc_rm_k0", "nldpc_rm_index",
                   "nldpc_rate_match", "nldpc_rate_recover", "nldpc_qam_points", "nldpc_qam_demap_ref",
                   "nldpc_qam_modulate", "nldpc_qam_demap", "nldpc_qam_channel_llr", "nldpc_crc_ref", "nldpc_crc_attach",
-                  "nldpc_crc_check")
+                  "nldpc_crc_check", "nldpc_tb_plan", "nldpc_tb_lifting_size", "nldpc_tb_er", "nldpc_tb_crc_ref",
+                  "nldpc_tb_workspace", "nldpc_tb_segment", "nldpc_tb_concat", "nldpc_tb_deconcat", "nldpc_tb_check")
 
 
 class NldpcCfg(ctypes.Structure):
@@ -67,6 +70,18 @@ class NldpcRm(ctypes.Structure):
         ("ncb", ctypes.c_int64),
         ("k0", ctypes.c_int64),
         ("E", ctypes.c_int64),
+    ]
+
+
+class NldpcTb(ctypes.Structure):
+    _fields_ = [
+        ("A", ctypes.c_int64),
+        ("tb_crc", ctypes.c_int32),
+        ("W", ctypes.c_int64),
+        ("C", ctypes.c_int32),
+        ("L", ctypes.c_int32),
+        ("Kp", ctypes.c_int64),
+        ("F", ctypes.c_int64),
     ]
 
 
@@ -129,6 +144,16 @@ def _declare(lib):
         "nldpc_crc_ref": (_i32, [_i32, _vp, _i64, _i64, ctypes.POINTER(ctypes.c_uint32)]),
         "nldpc_crc_attach": (_i32, [_i32, _vp, _i64, _i64, _i64, ctypes.c_uint64, _i64, _vp, _vp]),
         "nldpc_crc_check": (_i32, [_i32, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp]),
+        "nldpc_tb_plan": (_i32, [_i64, _i32, _i64, _i64, ctypes.POINTER(NldpcTb)]),
+        "nldpc_tb_lifting_size": (_i32, [_i32, _i64, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+        "nldpc_tb_er": (_i32, [_i64, _i32, _i32, _i32, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i32)]),
+        "nldpc_tb_crc_ref": (_i32, [ctypes.POINTER(NldpcTb), _vp, _i64, _vp, ctypes.POINTER(ctypes.c_uint32)]),
+        "nldpc_tb_workspace": (_i32, [ctypes.POINTER(NldpcTb), _i64, ctypes.POINTER(ctypes.c_size_t)]),
+        "nldpc_tb_segment": (_i32, [ctypes.POINTER(NldpcTb), _vp, _i64, _vp, _vp]),
+        "nldpc_tb_concat": (_i32, [_i32, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _vp, _vp]),
+        "nldpc_tb_deconcat": (_i32, [_i32, _vp, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),
+        "nldpc_tb_check": (_i32, [ctypes.POINTER(NldpcTb), _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  ctypes.c_size_t, _vp]),
         "nldpc_awgn_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp]),
         "nldpc_channel_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp, _i64, _i64,
                                      ctypes.c_float, _i64, _i64, ctypes.c_float, _vp]),
