@@ -448,7 +448,9 @@ __device__ __forceinline__ void cn_backward(const float (&m)[DC], const float (&
             if (l < d) {
                 const float xc = clampf(m[l], lo, hi);
                 const float t = tanh_ref(fmul(-0.5f, xc), sp.tanh);
-                gm[l] = graw[l] * (1.f - t * t) * -0.5f * in_range(m[l], lo, hi);
+                // torch's tanh backward evaluates 1 - t^2 with ONE rounding (a fused multiply-add in ATen's CPU kernel,
+                // vector and scalar path alike); t near +-1 makes the two-rounding form differ from it by percents
+                gm[l] = graw[l] * __fmaf_rn(-t, t, 1.f) * -0.5f * in_range(m[l], lo, hi);
             } else {
                 gm[l] = 0.f;
             }
@@ -675,7 +677,10 @@ __device__ __forceinline__ void cn_bwd_ms(LoadM&& load_m, float* lds, int stride
             }
             // (r6 sparse) s = sgn, or s = 0 with a zero magnitude, where g1 and gabs are +-0: (gabs * s) * sgn == gabs up
             // to the sign of a zero, which the +0-started sums g_at1 / g_at2 never keep
-            const float gmag = kSparse ? gabs : (gabs * s) * sgn;
+            // -- for QMS only: an MS minimum in (0, 1e-4) (a continuous input; no code value of a quantiser) makes the
+            // zero-fix correction mag = min - 1e-4 NEGATIVE, so x = mag * sgn and s have the sign opposite to sgn and
+            // (gabs * s) * sgn is -gabs: the argmins then get the gradient with the reference's flipped sign
+            const float gmag = (kSparse && KIND == NLDPC_QMS) ? gabs : (gabs * s) * sgn;
             if (sel) g_at2 += gmag;
             else g_at1 += gmag;
         }

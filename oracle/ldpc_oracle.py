@@ -85,6 +85,21 @@ def _tanh(x: torch.Tensor) -> torch.Tensor:
     return t + (ref - t).detach()
 
 
+def _atanh(x: torch.Tensor) -> torch.Tensor:
+    """torch.atanh (BoostedNeuralLDPCDecoder.py:408) through ATen's vectorised CPU loop for EVERY element.
+    ATen runs two vectors per step and hands the remaining numel % 32 elements of a call (and of every
+    thread's chunk of a call above its 32768-element grain) to the scalar libm atanh, which rounds differently
+    from the vector routine: a value would depend on where its codeword sits in the batch (seen at z=16,
+    B=19: the last 16 values of a 304 * d tensor with odd d).  The device evaluates the vector routine's
+    formula everywhere, and so does this: whole 64-element blocks, at most 16384 elements per call.  Every
+    fixture's tensors are a multiple of 32 elements already, so parity with the reference's outputs is unchanged."""
+    flat = x.reshape(-1)
+    n = flat.numel()
+    flat = torch.cat([flat, flat.new_zeros((-n) % 64)])
+    out = torch.cat([torch.atanh(c) for c in torch.split(flat, 16384)])
+    return out[:n].reshape(x.shape)
+
+
 class OracleGraph:
     """Edge tables of the lifted Tanner graph.  C-order edge index e (row-major over the base graph,
     ConnectingMatrix.py:92-99, 137-147) is the one used for messages and learned weights."""
@@ -204,9 +219,28 @@ def _cn_row_tile(g: OracleGraph, i: int, m_list):
     return m.unsqueeze(2) * w  # [B, Z, k(out), l(in)] == x_tile * W_even2odd^T restricted to the row
 
 
-def neural_forward(g: OracleGraph, xa: torch.Tensor, weights, biases):
+def _probe_cn(probe, ms, fixed=None):
+    """Coverage counters of one check row (tests/test_edge_inputs.py): inputs that are exactly 0 before the
+    zero fix, and check copies whose two smallest conditioned magnitudes (after the fix / the 10000 mask) tie."""
+    if probe is None:
+        return
+    with torch.no_grad():
+        m = torch.stack(ms, dim=2)
+        probe["cn_zero_inputs"] = probe.get("cn_zero_inputs", 0) + int((m == 0).sum())
+        a = torch.abs(torch.stack(fixed, dim=2) if fixed is not None else m)
+        a = torch.sort(a + 10000 * (1 - (a > 0).float()), dim=2)[0]
+        probe["cn_tied_minima"] = probe.get("cn_tied_minima", 0) + int((a[:, :, 0] == a[:, :, 1]).sum())
+
+
+def _probe_add(probe, key, mask):
+    if probe is not None:
+        probe[key] = probe.get(key, 0) + int(mask.sum())
+
+
+def neural_forward(g: OracleGraph, xa: torch.Tensor, weights, biases, probe=None):
     """NeuralLDPCDecoder.forward (NeuralLDPCDecoder.py:44-100).  xa [B, N, Z] fp32; weights/biases:
-    sequences of T tensors [E].  Returns the list of T outputs [B, N*Z]."""
+    sequences of T tensors [E].  Returns the list of T outputs [B, N*Z].  probe: an optional dict that
+    receives coverage counters of the intermediate values (they change nothing computed)."""
     B = xa.shape[0]
     Z = g.Z
     zero = torch.zeros((B, Z), dtype=torch.float32)
@@ -217,7 +251,9 @@ def neural_forward(g: OracleGraph, xa: torch.Tensor, weights, biases):
         cn = [None] * g.E
         for i in range(g.M):
             es = g.row_edges[i]
-            tile = _cn_row_tile(g, i, [_lift(v2c[e], int(g.shift[e])) for e in es])
+            ms = [_lift(v2c[e], int(g.shift[e])) for e in es]
+            _probe_cn(probe, ms)
+            tile = _cn_row_tile(g, i, ms)
             a = torch.abs(tile)
             x3 = torch.min(a + 10000 * (1 - (a > 0).float()), dim=3)[0]  # :74-75
             x4 = torch.ones_like(tile) - 2 * ((-tile) < 0).float()  # :77-78
@@ -227,6 +263,7 @@ def neural_forward(g: OracleGraph, xa: torch.Tensor, weights, biases):
         new = []
         for e in range(g.E):
             a = torch.abs(cn[e]) * weights[t][e] + biases[t][e]  # :89 (two roundings)
+            _probe_add(probe, "relu_killed", (a.detach() <= 0) & (cn[e].detach() != 0))
             a = a * (a > 0).float()
             new.append(a * torch.sign(cn[e]))
         c2v = new
@@ -236,12 +273,13 @@ def neural_forward(g: OracleGraph, xa: torch.Tensor, weights, biases):
 
 
 def boosted_forward(g: OracleGraph, xa: torch.Tensor, *, dtype: int, q: int, nw, iters, w_cn, w_ucn, w_vn,
-                    llr_lo=-20.0, llr_hi=20.0, fixed_iteration=(), fixed_iter_weight=None):
+                    llr_lo=-20.0, llr_hi=20.0, fixed_iteration=(), fixed_iter_weight=None, probe=None):
     """BoostedNeuralLDPCDecoder.forward (BoostedNeuralLDPCDecoder.py:260-538) for a tensor input and an
     iteration list that starts from the zero message state.
 
     w_cn / w_ucn / w_vn: callables it -> weight tensor (the value `fetch_param` returns) or None.
-    Returns the dict {iteration: output [B, N*Z]}."""
+    Returns the dict {iteration: output [B, N*Z]}.  probe: an optional dict that receives coverage counters
+    of the intermediate values (they change nothing computed)."""
     cn_s, ucn_s, vn_s = nw
     B = xa.shape[0]
     Z = g.Z
@@ -275,20 +313,23 @@ def boosted_forward(g: OracleGraph, xa: torch.Tensor, *, dtype: int, q: int, nw,
         cn = [None] * g.E
         for i in range(g.M):
             es = g.row_edges[i]
-            ms = []
+            ms, raw = [], []
             for e in es:
                 x2 = _lift(v2c[e], int(g.shift[e]))
                 x2 = quantize(x2, q) if dtype == QMS else torch.clamp(x2, llr_lo, llr_hi)  # :386-389
+                raw.append(x2)
                 if dtype in (MS, QMS):
                     x2 = x2 + 0.0001 * (1 - (torch.abs(x2) > 0).float())  # :391-393
                 ms.append(x2)
+            _probe_cn(probe, raw, ms)
             tile = _cn_row_tile(g, i, ms)
             if dtype == SP:
                 th = _tanh(torch.mul(-0.5, tile))  # :402
                 x3 = _prod_aten(torch.add(th, 1 - (torch.abs(th) > 0).float()),  # :403-404
                                 [int(g.vidx[e]) for e in es], g.E)
+                _probe_add(probe, "sp_clipped", x3.detach().abs() > 1 - 1e-7)
                 x3 = torch.clamp(x3, -1 + 1e-7, 1 - 1e-7)  # :406-407
-                x_out0 = torch.mul(-2.0, torch.atanh(x3))  # :408
+                x_out0 = torch.mul(-2.0, _atanh(x3))  # :408
             else:
                 a = torch.add(torch.abs(tile), torch.mul(10000.0, 1.0 - (torch.abs(tile) > 0).float()))
                 x3 = torch.min(a, dim=3)[0]  # :415
@@ -324,6 +365,7 @@ def boosted_forward(g: OracleGraph, xa: torch.Tensor, *, dtype: int, q: int, nw,
                 x1 = torch.abs(x0) * per_edge(wc, e)
             else:
                 raise UnboundLocalError("CN sharing code 5 is not handled by the reference forward (:505)")
+            _probe_add(probe, "relu_killed", (x1.detach() <= 0) & (x0.detach() != 0))
             x2 = x1 * (x1 > 0).float()
             x2 = quantize(x2, q) if dtype == QMS else torch.clamp(x2, llr_lo, llr_hi)
             new.append(x2 * torch.sign(x0))
@@ -332,6 +374,7 @@ def boosted_forward(g: OracleGraph, xa: torch.Tensor, *, dtype: int, q: int, nw,
             xa_origin = quantize(xa_origin, q)
         y = torch.stack([xa_origin[:, j, :] + _seq_sum([c2v[e] for e in g.col_edges[j]], zero)
                          for j in range(g.N)], 1)
+        _probe_add(probe, "posterior_at_clamp", (y.detach() <= llr_lo) | (y.detach() >= llr_hi))
         y = torch.clamp(y, llr_lo, llr_hi)
         outputs[t] = y.reshape(B, g.N * Z)
         if t in fixed_iteration:

@@ -85,7 +85,8 @@ def boosted_params(d, g, T, nw, fixed):
 
 @pytest.mark.parametrize("name", ["neural_cfg1_snr1_default", "neural_cfg1_snr2_default", "neural_cfg1_snr3_default",
                                   "neural_cfg1_snr4_default", "neural_cfg1_snr2_random",
-                                  "neural_bg2_z16_b16_t5_random", "neural_wimax_z24_b16_t20_random"])
+                                  "neural_bg2_z16_b16_t5_random", "neural_wimax_z24_b16_t20_random",
+                                  "neural_bg2_z16_edges"])
 @pytest.mark.parametrize("path", ["stream", "fused"])
 def test_neural_forward_matches_reference(golden, name, path):
     from nldpc.decode import KIND_NEURAL, DecodeCfg, decode

@@ -60,7 +60,7 @@ def _assert_out(o, ref, sp):
 
 
 @pytest.mark.parametrize("name", ["neural_cfg1_snr2_default", "neural_cfg1_snr2_random", "neural_bg2_z16_b16_t5_random",
-                                  "neural_wimax_z24_b16_t20_random"])
+                                  "neural_wimax_z24_b16_t20_random", "neural_bg2_z16_edges"])
 def test_neural_module_forward(golden, name):
     d = golden(name)
     model = _neural_model(d, name)
@@ -71,7 +71,8 @@ def test_neural_module_forward(golden, name):
         _assert_out(o, d["outputs"][t], False)
 
 
-@pytest.mark.parametrize("name", ["neural_bg2_z16_b16_t5_random", "neural_wimax_z24_b16_t20_random"])
+@pytest.mark.parametrize("name", ["neural_bg2_z16_b16_t5_random", "neural_wimax_z24_b16_t20_random",
+                                  "neural_bg2_z16_edges"])
 def test_neural_module_grads(golden, name):
     d = golden(name)
     model = _neural_model(d, name)
