@@ -502,6 +502,55 @@ int nldpc_tb_check(const nldpc_tb* plan, const float* llr, const uint8_t* bits, 
                    int32_t convention, const uint8_t* ref_tb, uint8_t* cb_ok, uint8_t* tb_ok, uint8_t* tb_out,
                    int64_t* counts, void* work, size_t work_bytes, void* stream);
 
+/* ---- Gold-sequence scrambling (additive to ABI 4): bit scrambling with the length-31 Gold sequence of 3GPP TS 38.211
+ *      §5.2.1 (PUSCH §6.3.1.1, PDSCH §7.3.1.1), the step between code-block concatenation (nldpc_tb_concat) and the
+ *      mapper (nldpc_qam_*), and its inverse on the LLRs in front of nldpc_tb_deconcat / nldpc_rate_recover.  The
+ *      reference has no counterpart.  The arithmetic is the inline functions of csrc/nldpc_gold.h on host and device.
+ *   Sequence: x1(n+31) = x1(n+3) ^ x1(n), x1(0) = 1, x1(1..30) = 0; x2(n+31) = x2(n+3) ^ x2(n+2) ^ x2(n+1) ^ x2(n),
+ *      x2(i) = (c_init >> i) & 1 for i < 31; c(n) = x1(n + 1600) ^ x2(n + 1600); 0 <= c_init < 2^31.
+ *   Packing: a sequence of E bits is Wc = ceil(E / 32) words of 32 bits, bit n in bit n & 31 of word n >> 5 (least
+ *      significant first); the bits at and beyond E in the last word are 0.  A table is seq[n_seq][Wc]; row b of a batch
+ *      uses sequence (b_offset + b) mod n_seq: n_seq = 1 is one sequence for every row, and a table with one sequence
+ *      per transport block shards as the Philox streams do.
+ *   nldpc_gold_cinit (host only): *c_init = rnti * 2^15 + q * 2^14 + n_id.  NLDPC_EINVAL unless 0 <= rnti < 2^16, q in
+ *      {0, 1}, 0 <= n_id < 1024, c_init non-NULL.
+ *   nldpc_gold_ref (host only, no device): c[i] = c(n0 + i), i < n, as bytes 0 / 1.  It jumps to n0 (x^(n0 + 1600) mod
+ *      the register's polynomial by squaring: with r = x^n mod p, x(n + j) = XOR over the k with r_k = 1 of x(k + j), so
+ *      the state at n follows from r and the register's first 61 bits), then steps 32 bits at a time; it does not run
+ *      from 0.  NLDPC_EINVAL: c_init >= 2^31, n0 < 0, n < 1, n0 + n > 2^31, c NULL.
+ *   nldpc_gold_sequence: c_init device int32 [n_seq] -> seq device [n_seq][Wc], written in full.  Of each c_init entry
+ *      the low 31 bits are used (a negative entry cannot be reported by a launch that does not synchronise).  One
+ *      kernel; a thread jumps to its run of words as nldpc_gold_ref does, so the words do not depend on the run length
+ *      or the grid.  NLDPC_EINVAL: n_seq < 1, E < 1, E >= 2^31, a NULL pointer, a pointer off a 4-byte boundary;
+ *      NLDPC_EUNSUPPORTED: n_seq * Wc >= 2^31.
+ *   nldpc_scramble: out[b][i] = (f[b][i] != 0) ^ c_s(i) as 0 / 1, s = (b_offset + b) mod n_seq; f, out uint8 [B][E], any
+ *      start address; f NULL = the all-zero word (out is the sequence unpacked); out == f (in place) is allowed, any
+ *      other overlap is the caller's error.
+ *   nldpc_descramble_llr: out[b][i] = llr[b][i] with its sign bit XORed with c_s(i), an integer operation on the bit
+ *      pattern: -0, infinities and NaN payloads pass with only the sign changed, and applying it twice is the identity
+ *      bit for bit.  llr, out fp32 [B][E]; in place is allowed.
+ *   nldpc_qam_channel_llr_scrambled: nldpc_qam_channel_llr with f ^ c going into the mapper and the sign flip coming
+ *      out, in one kernel: llr is bit for bit nldpc_descramble_llr(nldpc_qam_channel_llr(nldpc_scramble(f))) -- counters,
+ *      tag and Box-Muller unchanged, a symbol's noise is the one nldpc_qam_channel_llr draws for it --, and sym_out
+ *      (nullable) receives the noisy symbols of the scrambled bits (what is on the air).  f NULL = the all-zero word,
+ *      which then visits every constellation point while the decoder still sees "bit 0 sent" everywhere.  The argument
+ *      rules are those of nldpc_qam_channel_llr, and seq non-NULL and 4-byte aligned, n_seq >= 1.
+ *   For the three table users: NLDPC_EINVAL: seq NULL or off a 4-byte boundary, n_seq < 1, B < 1, E < 1, E >= 2^31,
+ *      b_offset < 0, a NULL required pointer, a float pointer off a 4-byte boundary; NLDPC_EUNSUPPORTED: B or b_offset
+ *      >= 2^31, n_seq * Wc >= 2^31.  seq must have Wc = ceil(E / 32) words per row (not checkable from a pointer).
+ *   All launches are stream-ordered on the current device, synchronise and allocate nothing and write nothing outside
+ *      seq / out / llr / sym_out. */
+int nldpc_gold_cinit(int32_t rnti, int32_t q, int32_t n_id, uint32_t* c_init);
+int nldpc_gold_ref(uint32_t c_init, int64_t n0, int64_t n, uint8_t* c);
+int nldpc_gold_sequence(const int32_t* c_init, int64_t n_seq, int64_t E, uint32_t* seq, void* stream);
+int nldpc_scramble(const uint8_t* f, const uint32_t* seq, int64_t n_seq, int64_t B, int64_t E, int64_t b_offset,
+                   uint8_t* out, void* stream);
+int nldpc_descramble_llr(const float* llr, const uint32_t* seq, int64_t n_seq, int64_t B, int64_t E, int64_t b_offset,
+                         float* out, void* stream);
+int nldpc_qam_channel_llr_scrambled(int32_t qm, int32_t method, const uint8_t* f, int64_t B, int64_t E, float sigma,
+                                    uint64_t seed, int64_t b_offset, const uint32_t* seq, int64_t n_seq, float* llr,
+                                    float* sym_out, void* stream);
+
 /* ---- benchmark instrumentation: per-kernel HIP-event timing of nldpc_forward / nldpc_backward
  *   launches.  nldpc_profile_begin arms a recorder for up to `capacity` launches (not thread-safe);
  *   nldpc_profile_end synchronises on the recorded events and returns summed milliseconds and

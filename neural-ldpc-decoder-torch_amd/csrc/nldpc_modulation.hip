@@ -1,6 +1,6 @@
 // QAM modulation and soft demapping (3GPP TS 38.211 §5.1.3-5.1.6; include/nldpc.h): nldpc_qam_points,
-// nldpc_qam_demap_ref (host), nldpc_qam_modulate, nldpc_qam_demap, nldpc_qam_channel_llr.  The arithmetic is the inline
-// functions of nldpc_qam.h on both sides.
+// nldpc_qam_demap_ref (host), nldpc_qam_modulate, nldpc_qam_demap, nldpc_qam_channel_llr, nldpc_qam_channel_llr_scrambled.
+// The arithmetic is the inline functions of nldpc_qam.h (and nldpc_gold.h) on both sides.
 //
 // Bits, symbols and LLRs of a batch are flat streams ([B][E] bytes, [B][S][2] and [B][E] floats, all contiguous), so a
 // row plays no part: a thread owns one PAIR of consecutive symbols -- in the fused kernel the two symbols of one Philox
@@ -13,6 +13,7 @@
 // outside the outputs is touched.
 #include <hip/hip_runtime.h>
 
+#include "nldpc_gold.h"
 #include "nldpc_internal.h"
 #include "nldpc_philox.h"
 #include "nldpc_qam.h"
@@ -200,7 +201,78 @@ __global__ __launch_bounds__(kQamThreads) void qam_channel_kernel(QamArgs a) {
     if (a.sym) qam_store_pair<2>(a.sym, p, r, nullptr);
 }
 
+// ---------------------------------------------------------------- the same with Gold-sequence scrambling in flight
+// (nldpc_qam_channel_llr_scrambled): f ^ c goes into the mapper and the LLRs leave with their sign bits XORed with c, so
+// the caller sees the LLRs of f while the symbols on the air are those of the scrambled bits.  The counter, the noise and
+// the store path are qam_channel_kernel's.  A symbol's qm sequence bits come from the packed table [n_seq][Wc]
+// (gold_bits); its row and in-row index follow from its batch-local index with one division and one remainder per thread:
+// the odd symbol is divided, the even one is its predecessor (the last symbol of the row before, with the sequence before,
+// when the pair straddles two rows).
+struct QamScrArgs {
+    QamArgs q;
+    const uint32_t* seq;  // [n_seq][Wc]
+    int64_t n_seq, Wc;
+    int64_t S;         // symbols per row
+    int64_t b_offset;  // row b uses sequence (b_offset + b) mod n_seq
+};
+
+// qam_map_pair with bit i of the symbol XORed with bit i of m
+template <int H>
+__device__ __forceinline__ void qam_map_pair_scr(const uint32_t* w, int j, uint32_t m, float& li, float& lq) {
+    constexpr int QM = 2 * H;
+    uint32_t ci, cq;
+    const auto bit = [&](int i) {
+        const bool f = ((w[(j * QM + i) >> 2] >> (8 * ((j * QM + i) & 3))) & 0xFFu) != 0;
+        return f != (((m >> i) & 1u) != 0);
+    };
+    qam_labels(H, bit, ci, cq);
+    li = qam_level(H, ci);
+    lq = qam_level(H, cq);
+}
+
+template <int H, int METHOD>
+__global__ __launch_bounds__(kQamThreads) void qam_channel_scr_kernel(QamScrArgs s) {
+    constexpr int QM = 2 * H;
+    const QamArgs& a = s.q;
+    const QamPair p = qam_pair(a);
+    if (!p.own0 && !p.own1) return;
+    const U4 c = philox4x32_10(U4{(uint32_t)p.g, (uint32_t)(p.g >> 32), kQamTag, 0u}, (uint32_t)a.seed,
+                               (uint32_t)(a.seed >> 32));
+    const double rad0 = sqrt(-2.0 * log(u01(c.x))), th0 = 6.283185307179586 * u01(c.y);
+    const double rad1 = sqrt(-2.0 * log(u01(c.z))), th1 = 6.283185307179586 * u01(c.w);
+    const double n[4] = {rad0 * cos(th0), rad0 * sin(th0), rad1 * cos(th1), rad1 * sin(th1)};
+    // the odd symbol's row b1 and in-row index j1 (loc + 1 >= 0 always), its sequence i1 = (b_offset + b1) mod n_seq
+    // (b_offset + b1 < 2^32, n_seq < 2^31), and from them the even symbol's
+    const int64_t b1 = (p.loc + 1) / s.S, j1 = (p.loc + 1) - b1 * s.S;
+    const uint32_t i1 = s.n_seq == 1 ? 0u : (uint32_t)(s.b_offset + b1) % (uint32_t)s.n_seq;
+    const uint32_t i0 = j1 ? i1 : (i1 ? i1 - 1u : (uint32_t)s.n_seq - 1u);
+    const int64_t j0 = j1 ? j1 - 1 : s.S - 1;
+    uint32_t m[2] = {0u, 0u};
+    if (p.own0) m[0] = gold_bits(s.seq + (int64_t)i0 * s.Wc, j0 * QM, QM);
+    if (p.own1) m[1] = gold_bits(s.seq + (int64_t)i1 * s.Wc, j1 * QM, QM);
+    uint32_t w[H];
+    qam_load_bits<H>(a.f, p, w);
+    float l[4], r[4];
+    qam_map_pair_scr<H>(w, 0, m[0], l[0], l[1]);
+    qam_map_pair_scr<H>(w, 1, m[1], l[2], l[3]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) r[q] = (float)((double)l[q] + a.sigma * n[q]);
+    float lvl[1 << H], v[2 * QM];
+    qam_levels<H>(lvl);
+    qam_demap_symbol<H, METHOD>(lvl, r[0], r[1], a.w, v);
+    qam_demap_symbol<H, METHOD>(lvl, r[2], r[3], a.w, v + QM);
+#pragma unroll
+    for (int i = 0; i < 2 * QM; ++i) v[i] = __uint_as_float(__float_as_uint(v[i]) ^ (((m[i / QM] >> (i % QM)) & 1u) << 31));
+    qam_store_pair<QM>(a.llr, p, v, qam_stage<H>());
+    if (a.sym) qam_store_pair<2>(a.sym, p, r, nullptr);
+}
+
 typedef void (*QamKernel)(QamArgs);
+typedef void (*QamScrKernel)(QamScrArgs);
+static const QamScrKernel kChannelScr[4][2] = {{qam_channel_scr_kernel<1, 0>, qam_channel_scr_kernel<1, 1>},
+                                               {qam_channel_scr_kernel<2, 0>, qam_channel_scr_kernel<2, 1>},
+                                               {qam_channel_scr_kernel<3, 0>, qam_channel_scr_kernel<3, 1>},
+                                               {qam_channel_scr_kernel<4, 0>, qam_channel_scr_kernel<4, 1>}};
 static const QamKernel kModulate[4] = {qam_modulate_kernel<1>, qam_modulate_kernel<2>, qam_modulate_kernel<3>,
                                        qam_modulate_kernel<4>};
 static const QamKernel kDemap[4][2] = {{qam_demap_kernel<1, 0>, qam_demap_kernel<1, 1>},
@@ -226,9 +298,10 @@ static const QamHostDemap kDemapHost[4][2] = {{qam_demap_host<1, 0>, qam_demap_h
 
 static float qam_weight(float sigma) { return (float)(1.0 / (2.0 * (double)sigma * (double)sigma)); }
 
-// one thread per pair of the symbols [first, first + total)
-static int qam_launch(const char* who, QamKernel k, const QamArgs& a, void* stream) {
-    const int64_t pairs = ((a.first + a.total + 1) >> 1) - (a.first >> 1);
+// one thread per pair of the symbols [first, first + total); a = the kernel's argument, q its QamArgs
+template <class Kernel, class Args>
+static int qam_launch(const char* who, Kernel k, const Args& a, const QamArgs& q, void* stream) {
+    const int64_t pairs = ((q.first + q.total + 1) >> 1) - (q.first >> 1);
     const int64_t blocks = (pairs + kQamThreads - 1) / kQamThreads;
     if (blocks > 0x7FFFFFFF) return fail(NLDPC_EUNSUPPORTED, std::string(who) + ": too large");
     hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(kQamThreads), 0, static_cast<hipStream_t>(stream), a);
@@ -272,7 +345,7 @@ extern "C" int nldpc_qam_modulate(int32_t qm, const uint8_t* f, int64_t B, int64
     a.f = f;
     a.sym = sym;
     a.total = B * (E / qm);
-    return qam_launch("nldpc_qam_modulate", kModulate[qm / 2 - 1], a, stream);
+    return qam_launch("nldpc_qam_modulate", kModulate[qm / 2 - 1], a, a, stream);
 }
 
 extern "C" int nldpc_qam_demap(int32_t qm, int32_t method, float sigma, const float* sym, int64_t B, int64_t S,
@@ -289,20 +362,20 @@ extern "C" int nldpc_qam_demap(int32_t qm, int32_t method, float sigma, const fl
     a.llr = llr;
     a.total = B * S;
     a.w = qam_weight(sigma);
-    return qam_launch("nldpc_qam_demap", kDemap[qm / 2 - 1][method], a, stream);
+    return qam_launch("nldpc_qam_demap", kDemap[qm / 2 - 1][method], a, a, stream);
 }
 
-extern "C" int nldpc_qam_channel_llr(int32_t qm, int32_t method, const uint8_t* f, int64_t B, int64_t E, float sigma,
-                                     uint64_t seed, int64_t b_offset, float* llr, float* sym_out, void* stream) {
-    if (!qam_order_ok(qm)) return fail(NLDPC_EINVAL, "nldpc_qam_channel_llr: qm is 2, 4, 6 or 8");
-    if (method != 0 && method != 1) return fail(NLDPC_EINVAL, "nldpc_qam_channel_llr: method is 0 (max-log) or 1 (log-MAP)");
-    if (!(sigma > 0.f)) return fail(NLDPC_EINVAL, "nldpc_qam_channel_llr: sigma must be positive");
-    if (!llr || B <= 0 || E <= 0 || b_offset < 0) return fail(NLDPC_EINVAL, "nldpc_qam_channel_llr: bad argument");
-    if (E >= (int64_t)1 << 31 || E % qm != 0) return fail(NLDPC_EINVAL, "nldpc_qam_channel_llr: E must be below 2^31 and a multiple of qm");
-    if (misaligned4(llr) || misaligned4(sym_out)) return fail(NLDPC_EINVAL, "nldpc_qam_channel_llr: llr and sym_out must be 4-byte aligned");
-    if (B >= (int64_t)1 << 31 || b_offset >= (int64_t)1 << 31) return fail(NLDPC_EUNSUPPORTED, "nldpc_qam_channel_llr: too large");
+// the argument rules of the two fused channels, and their QamArgs
+static int qam_channel_args(const std::string& who, int32_t qm, int32_t method, const uint8_t* f, int64_t B, int64_t E,
+                            float sigma, uint64_t seed, int64_t b_offset, float* llr, float* sym_out, QamArgs& a) {
+    if (!qam_order_ok(qm)) return fail(NLDPC_EINVAL, who + ": qm is 2, 4, 6 or 8");
+    if (method != 0 && method != 1) return fail(NLDPC_EINVAL, who + ": method is 0 (max-log) or 1 (log-MAP)");
+    if (!(sigma > 0.f)) return fail(NLDPC_EINVAL, who + ": sigma must be positive");
+    if (!llr || B <= 0 || E <= 0 || b_offset < 0) return fail(NLDPC_EINVAL, who + ": bad argument");
+    if (E >= (int64_t)1 << 31 || E % qm != 0) return fail(NLDPC_EINVAL, who + ": E must be below 2^31 and a multiple of qm");
+    if (misaligned4(llr) || misaligned4(sym_out)) return fail(NLDPC_EINVAL, who + ": llr and sym_out must be 4-byte aligned");
+    if (B >= (int64_t)1 << 31 || b_offset >= (int64_t)1 << 31) return fail(NLDPC_EUNSUPPORTED, who + ": too large");
     const int64_t S = E / qm;
-    QamArgs a{};
     a.f = f;
     a.llr = llr;
     a.sym = sym_out;
@@ -311,5 +384,30 @@ extern "C" int nldpc_qam_channel_llr(int32_t qm, int32_t method, const uint8_t* 
     a.sigma = (double)sigma;
     a.w = qam_weight(sigma);
     a.seed = seed;
-    return qam_launch("nldpc_qam_channel_llr", kChannel[qm / 2 - 1][method], a, stream);
+    return NLDPC_OK;
+}
+
+extern "C" int nldpc_qam_channel_llr(int32_t qm, int32_t method, const uint8_t* f, int64_t B, int64_t E, float sigma,
+                                     uint64_t seed, int64_t b_offset, float* llr, float* sym_out, void* stream) {
+    QamArgs a{};
+    if (int rc = qam_channel_args("nldpc_qam_channel_llr", qm, method, f, B, E, sigma, seed, b_offset, llr, sym_out, a))
+        return rc;
+    return qam_launch("nldpc_qam_channel_llr", kChannel[qm / 2 - 1][method], a, a, stream);
+}
+
+extern "C" int nldpc_qam_channel_llr_scrambled(int32_t qm, int32_t method, const uint8_t* f, int64_t B, int64_t E,
+                                               float sigma, uint64_t seed, int64_t b_offset, const uint32_t* seq,
+                                               int64_t n_seq, float* llr, float* sym_out, void* stream) {
+    const char* who = "nldpc_qam_channel_llr_scrambled";
+    QamScrArgs s{};
+    if (int rc = qam_channel_args(who, qm, method, f, B, E, sigma, seed, b_offset, llr, sym_out, s.q)) return rc;
+    if (!seq || misaligned4(seq)) return fail(NLDPC_EINVAL, std::string(who) + ": seq must be non-NULL and 4-byte aligned");
+    if (n_seq < 1) return fail(NLDPC_EINVAL, std::string(who) + ": n_seq must be positive");
+    s.seq = seq;
+    s.n_seq = n_seq;
+    s.Wc = (E + 31) >> 5;
+    if (n_seq >= (int64_t)1 << 31 || n_seq * s.Wc >= (int64_t)1 << 31) return fail(NLDPC_EUNSUPPORTED, std::string(who) + ": too large");
+    s.S = E / qm;
+    s.b_offset = b_offset;
+    return qam_launch(who, kChannelScr[qm / 2 - 1][method], s, s.q, stream);
 }

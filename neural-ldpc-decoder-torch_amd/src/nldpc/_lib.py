@@ -35,6 +35,8 @@ EXPORTED = (
     "nldpc_crc_ref", "nldpc_crc_attach", "nldpc_crc_check",
     "nldpc_tb_plan", "nldpc_tb_lifting_size", "nldpc_tb_er", "nldpc_tb_crc_ref", "nldpc_tb_workspace", "nldpc_tb_segment",
     "nldpc_tb_concat", "nldpc_tb_deconcat", "nldpc_tb_check",
+    "nldpc_gold_cinit", "nldpc_gold_ref", "nldpc_gold_sequence", "nldpc_scramble", "nldpc_descramble_llr",
+    "nldpc_qam_channel_llr_scrambled",
 )
 
 
@@ -44,7 +46,9 @@ _ADDED_IN_ABI4 = ("nldpc_bce_loss_grad", "nldpc_bce_grad_unless_unit", "nldpc_co
                   "nldpc_rate_match", "nldpc_rate_recover", "nldpc_qam_points", "nldpc_qam_demap_ref",
                   "nldpc_qam_modulate", "nldpc_qam_demap", "nldpc_qam_channel_llr", "nldpc_crc_ref", "nldpc_crc_attach",
                   "nldpc_crc_check", "nldpc_tb_plan", "nldpc_tb_lifting_size", "nldpc_tb_er", "nldpc_tb_crc_ref",
-                  "nldpc_tb_workspace", "nldpc_tb_segment", "nldpc_tb_concat", "nldpc_tb_deconcat", "nldpc_tb_check")
+                  "nldpc_tb_workspace", "nldpc_tb_segment", "nldpc_tb_concat", "nldpc_tb_deconcat", "nldpc_tb_check",
+                  "nldpc_gold_cinit", "nldpc_gold_ref", "nldpc_gold_sequence", "nldpc_scramble", "nldpc_descramble_llr",
+                  "nldpc_qam_channel_llr_scrambled")
 
 
 class NldpcCfg(ctypes.Structure):
@@ -154,6 +158,13 @@ def _declare(lib):
         "nldpc_tb_deconcat": (_i32, [_i32, _vp, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),
         "nldpc_tb_check": (_i32, [ctypes.POINTER(NldpcTb), _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                   ctypes.c_size_t, _vp]),
+        "nldpc_gold_cinit": (_i32, [_i32, _i32, _i32, ctypes.POINTER(ctypes.c_uint32)]),
+        "nldpc_gold_ref": (_i32, [ctypes.c_uint32, _i64, _i64, _vp]),
+        "nldpc_gold_sequence": (_i32, [_vp, _i64, _i64, _vp, _vp]),
+        "nldpc_scramble": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+        "nldpc_descramble_llr": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+        "nldpc_qam_channel_llr_scrambled": (_i32, [_i32, _i32, _vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64,
+                                                   _vp, _i64, _vp, _vp, _vp]),
         "nldpc_awgn_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp]),
         "nldpc_channel_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp, _i64, _i64,
                                      ctypes.c_float, _i64, _i64, ctypes.c_float, _vp]),

@@ -6,7 +6,8 @@ modulate       sent bits [B, E] -> symbols [B, E/qm, 2] (I, Q) (nldpc_qam_modula
 demap          symbols -> LLRs [B, E] in the order of the bits, max-log or log-MAP (nldpc_qam_demap).
 qam_llr        the fused channel: bits -> symbols -> AWGN -> LLRs in one kernel (nldpc_qam_channel_llr); the noise comes
                from Philox-4x32-10 at the global symbol index, so a batch sharded over ranks draws the noise of the
-               unsharded batch.
+               unsharded batch.  scramble= a table of scrambling.sequence: Gold-sequence scrambling in front of the
+               mapper and descrambling behind the demapper inside the same kernel.
 sigma_for      Eb/N0 -> noise standard deviation per real dimension at unit symbol energy.
 
 A symbol carries qm consecutive bits of a row, f[b, s*qm : (s+1)*qm]: the grouping RateMatch(qm=qm)'s interleaver
@@ -115,12 +116,16 @@ def demap(sym: torch.Tensor, qm: int, sigma: float, *, method: str = "maxlog",
 
 def qam_llr(f: torch.Tensor | None, qm: int, sigma: float, *, B: int | None = None, E: int | None = None,
             seed: int = 2042, b_offset: int = 0, method: str = "maxlog", device=None,
-            out: torch.Tensor | None = None, return_symbols: bool | torch.Tensor = False):
+            out: torch.Tensor | None = None, return_symbols: bool | torch.Tensor = False,
+            scramble: torch.Tensor | None = None):
     """fp32 [B, E] LLRs of the bits f (contiguous uint8 [B, E] on the device, or None: the all-zero word, with B and E
     given) sent as 2^qm-QAM symbols over AWGN of standard deviation sigma per real dimension and demapped, in one
     kernel.  The noise of codeword b is that of codeword b_offset + b of the stream of `seed`.  return_symbols: True
     (or a contiguous fp32 [B, E/qm, 2] tensor to fill) also returns the noisy symbols, as (llr, symbols); the LLRs are
-    bit for bit demap(symbols, qm, sigma, method=method)."""
+    bit for bit demap(symbols, qm, sigma, method=method).  scramble: a table of scrambling.sequence for rows of E bits:
+    f ^ c goes into the mapper and the LLRs come out descrambled (nldpc_qam_channel_llr_scrambled), bit for bit
+    scrambling.descramble(qam_llr(scrambling.scramble(f, table), ...), table) with b_offset also selecting the row's
+    sequence; the symbols returned are then those of the scrambled bits, and the LLRs are no longer their demap."""
     qm, m, sigma = _order(qm), _method(method), _sigma(sigma)
     if f is not None:
         dev, fB, fE = _bits(f, qm)
@@ -146,6 +151,15 @@ def qam_llr(f: torch.Tensor | None, qm: int, sigma: float, *, B: int | None = No
         sym = _out(return_symbols, (B, E // qm, 2), dev, "return_symbols")
     elif return_symbols:
         sym = torch.empty((B, E // qm, 2), dtype=torch.float32, device=dev)
+    if scramble is not None:
+        from .scrambling import _on, _table
+        n_seq = _table(scramble, E)
+        _on(dev, scramble)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().nldpc_qam_channel_llr_scrambled(
+                qm, m, _lib.ptr(f), B, E, sigma, int(seed) & (2 ** 64 - 1), int(b_offset), scramble.data_ptr(), n_seq,
+                out.data_ptr(), _lib.ptr(sym), _lib.stream_of(dev)), "nldpc_qam_channel_llr_scrambled")
+        return out if sym is None else (out, sym)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().nldpc_qam_channel_llr(qm, m, _lib.ptr(f), B, E, sigma, int(seed) & (2 ** 64 - 1),
                                                     int(b_offset), out.data_ptr(), _lib.ptr(sym),
