@@ -551,6 +551,56 @@ int nldpc_qam_channel_llr_scrambled(int32_t qm, int32_t method, const uint8_t* f
                                     uint64_t seed, int64_t b_offset, const uint32_t* seq, int64_t n_seq, float* llr,
                                     float* sym_out, void* stream);
 
+/* ---- Flat block fading with perfect CSI for the QAM channel (additive to ABI 4): nldpc_qam_channel_llr with a real gain
+ *      g >= 0 between the mapper and the noise -- the channel's magnitude after the receiver's exact phase de-rotation,
+ *      under which circular noise stays circular -- and a demapper that knows g.  The reference has no counterpart.  The
+ *      arithmetic is the inline functions of csrc/nldpc_fading.h (and nldpc_qam.h) on host and device.
+ *   Model, per real dimension: r = (float)((double)fl32(g * level) + (double)sigma * n), n exactly the normal
+ *      nldpc_qam_channel_llr draws for that symbol (same counter, tag "QAM1", same Box-Muller).  The demapper of the QAM
+ *      section runs unchanged on the levels fl32(g * l), one fp32 multiply per level, shared by I and Q of a symbol, with
+ *      the same w = (float)(1 / (2 sigma^2)).  g = 1 reproduces nldpc_qam_channel_llr / nldpc_qam_demap bit for bit;
+ *      g = 0 gives +-0 for every LLR of the symbol, both methods.  E[g^2] = 1 for drawn gains, so sigma means what it
+ *      means for AWGN.
+ *   Fading blocks: gains are constant over L >= 1 consecutive symbols of a row (the coherence length); n_blk =
+ *      ceil(S / L), the last block of a row may be short, blocks never span rows; L = 1 is fast fading, L >= S one gain
+ *      per row.  Symbol j of row b has the gain of global block Gf = (b_offset + b) * n_blk + j div L.  A gain table is
+ *      fp32 [B][n_blk], contiguous.
+ *   Drawn gains (Rician factor K >= 0 as a double; K = 0 is Rayleigh and no special case): Philox-4x32-10 with key
+ *      (lo32(seed), hi32(seed)) at counter (lo32(Gf >> 1), hi32(Gf >> 1), 0x46414431 "FAD1", 0); words (x, y) serve an
+ *      even Gf, (z, w) an odd one.  With the block's words (r0, r1), u = (word + 1) / 2^32, all in double without FMA:
+ *      rad = sqrt(-2 log u(r0)), th = 6.283185307179586 u(r1), a = rad cos(th), b = rad sin(th),
+ *      mu = sqrt(K / (K + 1)), s = sqrt(1 / (2 (K + 1))), g = (float)sqrt((mu + s a)^2 + (s b)^2), rounded to fp32
+ *      once.  b_offset moves the gain stream as it moves the noise stream: a shard draws the unsharded batch's gains.
+ *   Given gains must be finite and >= 0; nothing checks that (it would take a pass over the table), and a negative,
+ *      infinite or NaN gain gives LLRs of no meaning, never a write outside the outputs.
+ *   nldpc_fading_gain_ref (host only, no device): g[i] from the word pair (words[2i], words[2i+1]), i < n.
+ *   nldpc_qam_demap_csi_ref (host only, no device): sym host [B][S][2], gain host [B][n_blk] -> llr host [B][S*qm].
+ *   nldpc_fading_gains: the drawn table g [B][n_blk] of the rows b_offset .. b_offset + B - 1, written in full.
+ *   nldpc_qam_demap_csi: sym [B][S][2] and gain [B][n_blk] -> llr [B][S*qm].
+ *   nldpc_qam_fading_channel_llr: bits -> (scramble) -> levels -> gain -> noise -> CSI demap -> (descramble) in one
+ *      kernel.  f NULL = the all-zero word.  gain_in NULL draws the gains (K, seed), else it is the table and K is only
+ *      checked.  seq NULL = no scrambling, else the table of nldpc_gold_sequence for rows of E bits, n_seq sequences,
+ *      used as nldpc_qam_channel_llr_scrambled uses it (n_seq is ignored without seq).  llr is bit for bit
+ *      nldpc_qam_demap_csi of the symbols and gains it returns (and of those descrambled with seq): sym_out (nullable)
+ *      receives the r, [B][S][2]; gain_out (nullable) the gains, [B][n_blk], written in full, bit for bit
+ *      nldpc_fading_gains when drawn, a copy of gain_in when given.  gain_out must not overlap gain_in.
+ *   NLDPC_EINVAL: the rules of nldpc_qam_demap (the two demappers) and nldpc_qam_channel_llr (the fused channel), and
+ *      L < 1, K negative, infinite or NaN, B * n_blk >= 2^31, n_blk < 1 or >= 2^31 (nldpc_fading_gains), a NULL required
+ *      pointer, a float pointer or seq off a 4-byte boundary, n_seq < 1 with seq.  NLDPC_EUNSUPPORTED: B or b_offset
+ *      >= 2^31 (device calls), n_seq * Wc >= 2^31.
+ *   The three launches are stream-ordered on the current device, synchronise and allocate nothing and write nothing
+ *      outside g / llr / sym_out / gain_out. */
+int nldpc_fading_gain_ref(double K, const uint32_t* words, int64_t n, float* g);
+int nldpc_qam_demap_csi_ref(int32_t qm, int32_t method, float sigma, const float* sym, const float* gain, int64_t B,
+                            int64_t S, int64_t L, float* llr);
+int nldpc_fading_gains(double K, uint64_t seed, int64_t B, int64_t n_blk, int64_t b_offset, float* g, void* stream);
+int nldpc_qam_demap_csi(int32_t qm, int32_t method, float sigma, const float* sym, const float* gain, int64_t B,
+                        int64_t S, int64_t L, float* llr, void* stream);
+int nldpc_qam_fading_channel_llr(int32_t qm, int32_t method, const uint8_t* f, int64_t B, int64_t E, float sigma,
+                                 uint64_t seed, int64_t b_offset, int64_t L, double K, const float* gain_in,
+                                 const uint32_t* seq, int64_t n_seq, float* llr, float* sym_out, float* gain_out,
+                                 void* stream);
+
 /* ---- benchmark instrumentation: per-kernel HIP-event timing of nldpc_forward / nldpc_backward
  *   launches.  nldpc_profile_begin arms a recorder for up to `capacity` launches (not thread-safe);
  *   nldpc_profile_end synchronises on the recorded events and returns summed milliseconds and

@@ -9,6 +9,8 @@ Layers:
   nldpc.modulation  QAM modulation, soft demapping and the fused QAM/AWGN channel (TS 38.211 §5.1.3-5.1.6)
   nldpc.scrambling  Gold-sequence bit scrambling in front of the mapper and LLR descrambling behind the demapper
                     (TS 38.211 §5.2.1, §6.3.1.1, §7.3.1.1); modulation.qam_llr(scramble=) does both in the fused channel
+  nldpc.fading      flat block fading (Rician / Rayleigh, drawn or given gains) with perfect-CSI demapping for the QAM
+                    channel, fused like modulation.qam_llr and bit-identical to it at unit gain
   nldpc.crc         CRC attachment in front of the encoder, CRC checking and error accounting behind the decoder
                     (TS 38.212 §5.1)
   nldpc.transport   transport blocks: the TB CRC, code-block segmentation, per-block rate matching and concatenation,

@@ -37,6 +37,8 @@ EXPORTED = (
     "nldpc_tb_concat", "nldpc_tb_deconcat", "nldpc_tb_check",
     "nldpc_gold_cinit", "nldpc_gold_ref", "nldpc_gold_sequence", "nldpc_scramble", "nldpc_descramble_llr",
     "nldpc_qam_channel_llr_scrambled",
+    "nldpc_fading_gain_ref", "nldpc_qam_demap_csi_ref", "nldpc_fading_gains", "nldpc_qam_demap_csi",
+    "nldpc_qam_fading_channel_llr",
 )
 
 
@@ -48,7 +50,8 @@ _ADDED_IN_ABI4 = ("nldpc_bce_loss_grad", "nldpc_bce_grad_unless_unit", "nldpc_co
                   "nldpc_crc_check", "nldpc_tb_plan", "nldpc_tb_lifting_size", "nldpc_tb_er", "nldpc_tb_crc_ref",
                   "nldpc_tb_workspace", "nldpc_tb_segment", "nldpc_tb_concat", "nldpc_tb_deconcat", "nldpc_tb_check",
                   "nldpc_gold_cinit", "nldpc_gold_ref", "nldpc_gold_sequence", "nldpc_scramble", "nldpc_descramble_llr",
-                  "nldpc_qam_channel_llr_scrambled")
+                  "nldpc_qam_channel_llr_scrambled", "nldpc_fading_gain_ref", "nldpc_qam_demap_csi_ref",
+                  "nldpc_fading_gains", "nldpc_qam_demap_csi", "nldpc_qam_fading_channel_llr")
 
 
 class NldpcCfg(ctypes.Structure):
@@ -165,6 +168,15 @@ def _declare(lib):
         "nldpc_descramble_llr": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
         "nldpc_qam_channel_llr_scrambled": (_i32, [_i32, _i32, _vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64,
                                                    _vp, _i64, _vp, _vp, _vp]),
+        "nldpc_fading_gain_ref": (_i32, [ctypes.c_double, ctypes.POINTER(ctypes.c_uint32), _i64,
+                                         ctypes.POINTER(ctypes.c_float)]),
+        "nldpc_qam_demap_csi_ref": (_i32, [_i32, _i32, ctypes.c_float, ctypes.POINTER(ctypes.c_float),
+                                           ctypes.POINTER(ctypes.c_float), _i64, _i64, _i64,
+                                           ctypes.POINTER(ctypes.c_float)]),
+        "nldpc_fading_gains": (_i32, [ctypes.c_double, ctypes.c_uint64, _i64, _i64, _i64, _vp, _vp]),
+        "nldpc_qam_demap_csi": (_i32, [_i32, _i32, ctypes.c_float, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+        "nldpc_qam_fading_channel_llr": (_i32, [_i32, _i32, _vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i64,
+                                                ctypes.c_double, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
         "nldpc_awgn_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp]),
         "nldpc_channel_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp, _i64, _i64,
                                      ctypes.c_float, _i64, _i64, ctypes.c_float, _vp]),
