@@ -601,6 +601,94 @@ int nldpc_qam_fading_channel_llr(int32_t qm, int32_t method, const uint8_t* f, i
                                  const uint32_t* seq, int64_t n_seq, float* llr, float* sym_out, float* gain_out,
                                  void* stream);
 
+/* ---- MIMO spatial multiplexing with LMMSE soft detection (additive to ABI 4): one codeword over nt layers (3GPP TS 38.211
+ *      §6.3.1.3 / §7.3.1.3, identity precoding), an nr x nt flat block-fading channel and a linear MMSE detector in front
+ *      of the demapper of the QAM section.  The reference has no counterpart.  The arithmetic is the inline functions of
+ *      csrc/nldpc_mimo.h (and nldpc_qam.h, nldpc_fading.h) on host and device.
+ *   Geometry: nt in {1, 2, 4} layers, nr in {1, 2, 4} receive antennas, nr >= nt (six pairs).  A row of E bits is
+ *      S = E / qm symbols d(0 .. S-1), S a multiple of nt, and R = S / nt resource elements (REs): RE i carries
+ *      x_k(i) = d(nt i + k) on layer k.  In memory the layer mapping is the identity: an RE is nt consecutive symbols and
+ *      nt qm consecutive bits / LLRs.  Received samples are fp32 [B][R][nr][2] (re, im).
+ *   Fading blocks: the rules of the fading section counted in REs: H is constant over L >= 1 consecutive REs of a row,
+ *      n_blk = ceil(R / L) (1 when L >= R), blocks never span rows, RE i of row b has the matrix of global block
+ *      Gf = (b_offset + b) * n_blk + i div L.  A channel table is fp32 [B][n_blk][nr][nt][2], contiguous: h(r, t) is the
+ *      path from layer t to antenna r.
+ *   Complex arithmetic, everywhere below: (a + ib)(c + id) = (fl(fl(a c) - fl(b d)), fl(fl(a d) + fl(b c))), four rounded
+ *      products, one rounded difference and one rounded sum, no FMA; with a conjugated factor the signs move, the count
+ *      does not: conj(a + ib)(c + id) = (fl(fl(a c) + fl(b d)), fl(fl(a d) - fl(b c))) and (a + ib) conj(c + id) =
+ *      (fl(fl(a c) + fl(b d)), fl(fl(b c) - fl(a d))).  A sum over an index starts from its first term and adds the others in ascending order, real and
+ *      imaginary parts separately.  |z|^2 = fl(fl(re re) + fl(im im)).
+ *   Channel, fp32: s(r) = sum_t h(r, t) x_t, t ascending; each real component of y(r) is
+ *      (float)((double)s + (double)sigma * n), sigma the standard deviation per real dimension and receive antenna.
+ *   Noise: Philox-4x32-10 with key (lo32(seed), hi32(seed)) at counter (lo32(Gre), hi32(Gre), 0x4D494E31 "MIN1", q),
+ *      Gre = (b_offset + b) * R + i the global RE index, q < ceil(nr / 2) the antenna pair.  Words (x, y) give antenna 2q:
+ *      u = (word + 1) / 2^32, rad = sqrt(-2 log u(x)), th = 6.283185307179586 u(y), (n_re, n_im) = (rad cos th,
+ *      rad sin th), in double; words (z, w) give antenna 2q + 1 the same way (unused for nr = 1).  A shard draws the
+ *      noise of the unsharded batch.
+ *   Drawn channels: Rayleigh, i.i.d. CN(0, 1 / nt) entries, so the mean received energy per antenna and RE is 1 and
+ *      sigma keeps its per-receive-antenna meaning.  Entry e = r * nt + t of global block Gf: counter (lo32(Gf), hi32(Gf),
+ *      0x4D494831 "MIH1", e >> 1), words (x, y) for an even e, (z, w) for an odd one; with the entry's words (r0, r1),
+ *      rad and th as above, s = sqrt(1 / (2 nt)): re = (float)(s * (rad * cos th)), im = (float)(s * (rad * sin th)),
+ *      everything in double, each component rounded to fp32 once.  Rician entries, spatial correlation and precoding
+ *      are not drawn; a given table covers them.
+ *   Detector, per fading block, in double from the fp32 table (sigma the fp32 the ABI takes): n0 = 2 (sigma sigma),
+ *      q = 1 / n0.  With G = H^H H + n0 I the quantities wanted are W = G^-1 H^H (nt x nr), e_k = n0 [G^-1]_kk (the MMSE
+ *      of layer k), mu_k = 1 - e_k.  They are computed from the Cholesky factor of Gn = G / n0 = I + (H^H H) q, which
+ *      makes e_k = [Gn^-1]_kk a sum of squares (positive, no cancellation, no final product) and gives e_k = 1, mu_k = 0
+ *      exactly for a zero channel:
+ *        A(j,k) = sum_r conj(h(r,j)) h(r,k) for j >= k, r ascending; the diagonal is real, sum_r |h(r,k)|^2;
+ *        Gn(j,k) = A(j,k) q (each component) for j > k, Gn(k,k) = A(k,k) q + 1;
+ *        Gn = C C^H, C lower triangular, by columns j = 0 .. nt-1: d = Gn(j,j) - |C(j,0)|^2 - .. - |C(j,j-1)|^2 (subtracted
+ *          one by one, k ascending), C(j,j) = sqrt(d), c_j = 1 / C(j,j); for i > j: z = Gn(i,j) - C(i,0) conj(C(j,0)) - ..
+ *          - C(i,j-1) conj(C(j,j-1)) (one by one, k ascending, each component), C(i,j) = z c_j (each component);
+ *        M = C^-1: M(j,j) = c_j; for i > j: M(i,j) = -(sum_{k=j}^{i-1} C(i,k) M(k,j)) c_i (each component);
+ *        e_k = M(k,k)^2 + |M(k+1,k)|^2 + .. + |M(nt-1,k)|^2 (added one by one), mu_k = 1 - e_k, p = mu_k e_k,
+ *          w_k = 1 / p when p is positive and finite, else 0;
+ *        T(i,r) = sum_{k=0}^{i} M(i,k) conj(h(r,k));  W(k,r) = (sum_{i=k}^{nt-1} conj(M(i,k)) T(i,r)) q (each component).
+ *      W [nt][nr][2], mu [nt] and w [nt] are each rounded to fp32 once.  Only + - * / sqrt occur, in this order, so host,
+ *      device and a scalar float64 restatement agree bit for bit.
+ *   Equalise and demap, per RE, fp32: x^_k = sum_r W(k,r) y(r), r ascending; layer k is demapped by the demapper of the
+ *      QAM section, unchanged, on the levels fl32(mu_k * l) with the weight w_k in place of 1 / (2 sigma^2).  This is the
+ *      biased-LMMSE Gaussian approximation: x^_k = mu_k x_k + (interference + noise) of variance mu_k e_k, i.e.
+ *      mu_k e_k / 2 per real dimension.  For nt = nr = 1 and a real h = g it is analytically the CSI demapper of the
+ *      fading section: (x^ - mu l)^2 w = (y - g l)^2 / (2 sigma^2).  A zero channel gives +-0 for every LLR, both
+ *      methods, never NaN.  The LLRs of layers that interfere are not independent given the bits, and the residual
+ *      interference is not Gaussian; the decoder is handed them as if they were.
+ *   nldpc_mimo_entry_ref (host only, no device): the entry (h[2i], h[2i+1]) from the word pair (words[2i], words[2i+1]),
+ *      i < n, with s of nt.  NLDPC_EINVAL: nt not 1, 2 or 4, a NULL pointer, n < 1.
+ *   nldpc_mimo_filter_ref (host only, no device): h host [n][nr][nt][2] -> W [n][nt][nr][2], mu [n][nt], w [n][nt].
+ *   nldpc_mimo_detect_ref (host only, no device): y host [B][R][nr][2], h host [B][n_blk][nr][nt][2] -> llr host
+ *      [B][R * nt * qm].
+ *   nldpc_mimo_channels: the drawn table h [B][n_blk][nr][nt][2] of the rows b_offset .. b_offset + B - 1, in full.
+ *   nldpc_mimo_filter: h [B][n_blk][nr][nt][2] -> W [B][n_blk][nt][nr][2], mu [B][n_blk][nt], w [B][n_blk][nt].
+ *   nldpc_mimo_detect: y [B][R][nr][2] and h [B][n_blk][nr][nt][2] -> llr [B][R * nt * qm].
+ *   nldpc_mimo_channel_llr: bits -> (scramble) -> map -> H x -> noise -> filter -> equalise -> demap -> (descramble) in
+ *      one kernel.  f NULL = the all-zero word.  h_in NULL draws the channels (seed), else it is the table.  seq NULL = no
+ *      scrambling, else the table of nldpc_gold_sequence for rows of E bits, n_seq sequences, used as
+ *      nldpc_qam_channel_llr_scrambled uses it (n_seq is ignored without seq).  llr is bit for bit nldpc_mimo_detect of
+ *      the samples and channels it returns (and of those descrambled with seq): sym_out (nullable) receives y,
+ *      [B][R][nr][2]; h_out (nullable) the channels, written in full, bit for bit nldpc_mimo_channels when drawn, a copy
+ *      of h_in when given.  h_out must not overlap h_in.
+ *   NLDPC_EINVAL: qm not 2, 4, 6, 8; method not 0 / 1; sigma not positive; (nt, nr) not one of the six pairs; B, R, E or
+ *      n_blk < 1; b_offset < 0; L < 1; E >= 2^31 or not a multiple of qm; E / qm not a multiple of nt; R * nt * qm >= 2^31;
+ *      B * n_blk >= 2^31; a NULL required pointer; a float pointer or seq off a 4-byte boundary; n_seq < 1 with seq; h_out
+ *      overlapping h_in.  NLDPC_EUNSUPPORTED: B or b_offset >= 2^31 (device calls), n_seq * Wc >= 2^31.
+ *   The four launches are stream-ordered on the current device, synchronise and allocate nothing and write nothing
+ *      outside h / W / mu / w / llr / sym_out / h_out. */
+int nldpc_mimo_entry_ref(int32_t nt, const uint32_t* words, int64_t n, float* h);
+int nldpc_mimo_filter_ref(int32_t nt, int32_t nr, float sigma, const float* h, int64_t n, float* W, float* mu, float* w);
+int nldpc_mimo_detect_ref(int32_t qm, int32_t method, int32_t nt, int32_t nr, float sigma, const float* y, const float* h,
+                          int64_t B, int64_t R, int64_t L, float* llr);
+int nldpc_mimo_channels(int32_t nt, int32_t nr, uint64_t seed, int64_t B, int64_t n_blk, int64_t b_offset, float* h,
+                        void* stream);
+int nldpc_mimo_filter(int32_t nt, int32_t nr, float sigma, const float* h, int64_t B, int64_t n_blk, float* W, float* mu,
+                      float* w, void* stream);
+int nldpc_mimo_detect(int32_t qm, int32_t method, int32_t nt, int32_t nr, float sigma, const float* y, const float* h,
+                      int64_t B, int64_t R, int64_t L, float* llr, void* stream);
+int nldpc_mimo_channel_llr(int32_t qm, int32_t method, int32_t nt, int32_t nr, const uint8_t* f, int64_t B, int64_t E,
+                           float sigma, uint64_t seed, int64_t b_offset, int64_t L, const float* h_in,
+                           const uint32_t* seq, int64_t n_seq, float* llr, float* sym_out, float* h_out, void* stream);
+
 /* ---- benchmark instrumentation: per-kernel HIP-event timing of nldpc_forward / nldpc_backward
  *   launches.  nldpc_profile_begin arms a recorder for up to `capacity` launches (not thread-safe);
  *   nldpc_profile_end synchronises on the recorded events and returns summed milliseconds and

@@ -1,7 +1,7 @@
 // Philox-4x32-10 (Salmon et al. 2011) and the fp64 Box-Muller transform the device channels draw their noise with
 // (nldpc_aux.hip awgn_kernel and encode_kernel, nldpc_modulation.hip qam_channel_kernel).  Counter word 2 tells the
 // streams of one seed apart: 0 the BPSK noise, 0x454E4331 the encoder's info bits, 0x51414D31 the QAM noise, 0x46414431
-// the fading gains (nldpc_fading.h).
+// the fading gains (nldpc_fading.h), 0x4D494E31 and 0x4D494831 the MIMO noise and channel entries (nldpc_mimo.h).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -11,6 +11,8 @@ Layers:
                     (TS 38.211 §5.2.1, §6.3.1.1, §7.3.1.1); modulation.qam_llr(scramble=) does both in the fused channel
   nldpc.fading      flat block fading (Rician / Rayleigh, drawn or given gains) with perfect-CSI demapping for the QAM
                     channel, fused like modulation.qam_llr and bit-identical to it at unit gain
+  nldpc.mimo        spatial multiplexing of one codeword over 1, 2 or 4 layers, an nr x nt flat block-fading channel and
+                    LMMSE soft detection in front of the demapper, fused like fading.qam_llr (TS 38.211 §6.3.1.3)
   nldpc.crc         CRC attachment in front of the encoder, CRC checking and error accounting behind the decoder
                     (TS 38.212 §5.1)
   nldpc.transport   transport blocks: the TB CRC, code-block segmentation, per-block rate matching and concatenation,
