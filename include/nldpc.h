@@ -689,6 +689,64 @@ int nldpc_mimo_channel_llr(int32_t qm, int32_t method, int32_t nt, int32_t nr, c
                            float sigma, uint64_t seed, int64_t b_offset, int64_t L, const float* h_in,
                            const uint32_t* seq, int64_t n_seq, float* llr, float* sym_out, float* h_out, void* stream);
 
+/* ---- Exact max-log ML (joint) soft detection for the MIMO section (additive to ABI 4).  Geometry, fading blocks, complex
+ *      arithmetic, noise and channel streams are those of the MIMO section; only the detector differs.  The reference
+ *      has no counterpart.  The arithmetic is the inline functions of csrc/nldpc_mimo_ml.h (on nldpc_mimo.h and
+ *      nldpc_qam.h) on host and device.
+ *   Definition, per RE, with n0 = 2 sigma^2:  LLR(b) = (min_{x: b = 0} d(x) - min_{x: b = 1} d(x)) / n0,
+ *      d(x) = sum_r |y(r) - sum_t h(r,t) x_t|^2, x over all 2^(qm nt) symbol vectors; sign and bit order as
+ *      nldpc_mimo_detect (> 0 means bit 1, layer k's qm bits at k qm).  Max-log only: an exact log-MAP needs every
+ *      candidate.  No Gaussian approximation is involved: these are the max-log LLRs of y.
+ *   Reduction (exact): a pass enumerates the symbols of the layers in a set En and slices the remaining layer s, whose
+ *      best symbol given the others is the constellation point nearest to z = h_s^H r / |h_s|^2, r = y - sum_{t in En}
+ *      h_t x_t, Re and Im independently.  Since the sliced layer is unconstrained, the pass yields the exact minima for
+ *      every bit of every layer of En.  nt = 1: one pass, En = {0}, nothing sliced (2^qm candidates).  nt >= 2: pass A,
+ *      En = {0 .. nt-2}, s = nt-1, gives the layers 0 .. nt-2; pass B, En = {1 .. nt-1}, s = 0, gives layer nt-1
+ *      (2 * 2^(qm (nt-1)) candidates, no QR).
+ *   Supported: nt = 1 and 2 with qm = 2, 4, 6, 8; nt = 4 with qm = 2, 4.  nt = 4 with qm = 6 or 8 (2 * 64^3 and
+ *      2 * 256^3 candidates per RE) needs a tree search: NLDPC_EUNSUPPORTED.  nr follows the six (nt, nr) pairs.
+ *   Arithmetic, fp32, one rounding per operation, no FMA, complex products and ascending sums as the MIMO section
+ *      states them; A = the level scale of the QAM section, l(c) the level of label c:
+ *        sliced layer, per pass:  g = sum_r |h(r,s)|^2, r ascending;  q = fl(1 / g);  inv = q when g > 0 and q is finite,
+ *          else 0 (so |h_s|^2 = 0 gives z = 0).
+ *        candidate (labels (ci_t, cq_t) of the layers t of En):  res(r) = y(r), then for t in En ascending
+ *          res(r) = res(r) - h(r,t) (l(ci_t) + i l(cq_t)), each component: Re res - fl(fl(a li) - fl(b lq)),
+ *          Im res - fl(fl(a lq) + fl(b li)) with h(r,t) = a + i b.
+ *        slice:  num = sum_r conj(h(r,s)) res(r), r ascending;  z = (fl(Re num * inv), fl(Im num * inv));  per component
+ *          u = fl(fl(z K) + 2^(h-1)) with K = 1 / (2 A) = 0.70710678118654752, 1.5811388300841897, 3.2403703492039302,
+ *          6.5192024052026492 for qm = 2, 4, 6, 8 (evaluated in double, rounded to fp32 once);  j = floor(u) clamped
+ *          to 0 .. 2^h - 1 by (j > 0 ? j : 0) then (j < 2^h - 1 ? j : 2^h - 1), so a NaN gives 0;  x^ component =
+ *          fl((2 j - (2^h - 1)) A), which is the level of amplitude 2 j - (2^h - 1) as the QAM section computes it.
+ *          A near-tie can pick the neighbouring point; its metric exceeds the minimum over x_s by at most
+ *          4 A |h_s|^2 times the error of z per dimension.
+ *        metric:  e(r) = res(r) - h(r,s) x^ (each component as above; nt = 1: e = res);  d = sum_r |e(r)|^2, r ascending:
+ *          always the metric of a true candidate, whichever point the slice picked.
+ *        minima:  per layer t of En and label c, minI_t[c] = min of d over the candidates with ci_t = c, minQ_t[c]
+ *          likewise with cq_t = c; a minimum starts from +inf and takes d when d < minimum (a NaN never enters).  A
+ *          minimum is exact, so the order in which candidates are visited does not show.
+ *        LLR of bit k of the I dimension of layer t (bit 2k of the symbol; Q: bit 2k+1 from minQ_t):
+ *          fl(fl(min_{c: c_k = 0} minI_t[c] - min_{c: c_k = 1} minI_t[c]) w),  w = (float)(1 / (2 sigma sigma)) evaluated
+ *          in double from the fp32 sigma: the finish of the QAM section's max-log demapper on minI_t in place of d.
+ *      A zero channel gives every candidate the metric sum_r |y(r)|^2 and hence +0 for every LLR.  Host, device and
+ *      a float32 restatement agree bit for bit.
+ *   nldpc_mimo_detect_ml_ref (host only, no device): arguments as nldpc_mimo_detect_ref without method.
+ *   nldpc_mimo_detect_ml: y [B][R][nr][2] and h [B][n_blk][nr][nt][2] -> llr [B][R * nt * qm]; arguments as
+ *      nldpc_mimo_detect without method.
+ *   nldpc_mimo_channel_llr_ml: bits -> (scramble) -> map -> H x -> noise -> ML detect -> (descramble) in one kernel;
+ *      arguments as nldpc_mimo_channel_llr without method.  The noise and channel streams are those of
+ *      nldpc_mimo_channel_llr, so sym_out and h_out are bit for bit what that function returns for the same arguments,
+ *      and llr is bit for bit nldpc_mimo_detect_ml of them (descrambled with seq).
+ *   NLDPC_EINVAL: the rules of the MIMO section (without method).  NLDPC_EUNSUPPORTED: nt = 4 with qm >= 6; and as in
+ *      the MIMO section.  The launches are stream-ordered on the current device, synchronise and allocate nothing and
+ *      write nothing outside llr / sym_out / h_out. */
+int nldpc_mimo_detect_ml_ref(int32_t qm, int32_t nt, int32_t nr, float sigma, const float* y, const float* h, int64_t B,
+                             int64_t R, int64_t L, float* llr);
+int nldpc_mimo_detect_ml(int32_t qm, int32_t nt, int32_t nr, float sigma, const float* y, const float* h, int64_t B,
+                         int64_t R, int64_t L, float* llr, void* stream);
+int nldpc_mimo_channel_llr_ml(int32_t qm, int32_t nt, int32_t nr, const uint8_t* f, int64_t B, int64_t E, float sigma,
+                              uint64_t seed, int64_t b_offset, int64_t L, const float* h_in, const uint32_t* seq,
+                              int64_t n_seq, float* llr, float* sym_out, float* h_out, void* stream);
+
 /* ---- benchmark instrumentation: per-kernel HIP-event timing of nldpc_forward / nldpc_backward
  *   launches.  nldpc_profile_begin arms a recorder for up to `capacity` launches (not thread-safe);
  *   nldpc_profile_end synchronises on the recorded events and returns summed milliseconds and

@@ -11,11 +11,16 @@
 // so that each store instruction writes 64 consecutive 16-byte groups, non-temporally (as qam_store_pair of
 // nldpc_modulation.hip does for a pair); the last wave of the batch and a view off the boundary store element by
 // element.  Nothing outside the outputs is touched.
+//
+// Exact max-log ML detection (F14; the arithmetic is nldpc_mimo_ml.h): nldpc_mimo_detect_ml_ref (host),
+// nldpc_mimo_detect_ml, nldpc_mimo_channel_llr_ml, a second pair of kernels at the end of the namespace with the same
+// thread-per-RE mapping, arguments and stores.
 #include <hip/hip_runtime.h>
 
 #include "nldpc_gold.h"
 #include "nldpc_internal.h"
 #include "nldpc_mimo.h"
+#include "nldpc_mimo_ml.h"
 #include "nldpc_philox.h"
 
 namespace nldpc {
@@ -335,6 +340,132 @@ static int mimo_rows(const std::string& who, int64_t B, int64_t R, int64_t L, Mi
     r.n_blk = (int32_t)n_blk;
     return NLDPC_OK;
 }
+
+// ================================================================ exact max-log ML detection (nldpc_mimo_ml.h, F14)
+// One thread per RE, as above: the candidates of an RE are enumerated by its thread, two passes of M^(nt-1) for
+// nt >= 2.  MimoArgs, the staging area and the stores are those of the LMMSE kernels.
+
+// enumerate -> finish -> (descramble) -> store
+template <int H, int NT, int NR>
+__device__ __forceinline__ void mimo_ml_store(const MimoArgs& a, int64_t loc, const float* h, const float* y, uint32_t sm,
+                                              float* stage) {
+    constexpr int PER = NT * 2 * H;
+    float v[PER];
+    mimo_ml_detect<H, NT, NR>(h, y, mimo_ml_weight(a.sigma), v);
+#pragma unroll
+    for (int i = 0; i < PER; ++i) v[i] = __uint_as_float(__float_as_uint(v[i]) ^ (((sm >> i) & 1u) << 31));
+    mimo_store_run<PER>(a.llr, loc, v, stage);
+}
+
+// ---------------------------------------------------------------- nldpc_mimo_detect_ml: y and H -> LLRs
+template <int H, int NT, int NR>
+__global__ __launch_bounds__(kMimoThreads) void mimo_ml_detect_kernel(MimoArgs a) {
+    constexpr int PER = NT * 2 * H;
+    const int64_t loc = (int64_t)blockIdx.x * kMimoThreads + threadIdx.x;
+    if (loc >= a.total) return;
+    const MimoIdx x = mimo_index(loc, a.r.R, a.r.L);
+    float h[2 * NR * NT], y[2 * NR];
+    mimo_load_block<NT, NR>(a.h, mimo_block(x, a.r.n_blk), h);
+#pragma unroll
+    for (int e = 0; e < 2 * NR; ++e) y[e] = a.y_in[loc * (2 * NR) + e];
+    mimo_ml_store<H, NT, NR>(a, loc, h, y, 0u, mimo_stage<PER>());
+}
+
+// ---------------------------------------------------------------- nldpc_mimo_channel_llr_ml, the fused channel:
+// bits -> (scramble) -> map -> H x -> noise -> ML detect -> (descramble).  The transmit side is mimo_channel_kernel's,
+// statement for statement (the same streams, so the same samples and channels)
+template <int H, int NT, int NR>
+__global__ __launch_bounds__(kMimoThreads) void mimo_ml_channel_kernel(MimoArgs a) {
+    constexpr int QM = 2 * H, PER = NT * QM, PERY = 2 * NR, PERS = PER > PERY ? PER : PERY;
+    const int64_t loc = (int64_t)blockIdx.x * kMimoThreads + threadIdx.x;
+    if (loc >= a.total) return;
+    const MimoIdx x = mimo_index(loc, a.r.R, a.r.L);
+    const int64_t blk = mimo_block(x, a.r.n_blk);
+    float h[2 * NR * NT];
+    if (a.h) mimo_load_block<NT, NR>(a.h, blk, h);  // (a uniform branch)
+    else mimo_draw<NT, NR>(mimo_global(a.b_offset, x, a.r.n_blk), a.scale, a.seed, h);
+    if (a.h_out && mimo_first(x, a.r.L)) {
+        float* dst = a.h_out + blk * (2 * NR * NT);
+#pragma unroll
+        for (int e = 0; e < 2 * NR * NT; ++e) dst[e] = h[e];
+    }
+    uint32_t fb = 0u, sm = 0u;
+    if (a.f) {
+        const uint8_t* src = a.f + loc * PER;
+        if (PER % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 3) == 0) {
+#pragma unroll
+            for (int q = 0; q < PER / 4; ++q) {
+                const uint32_t wd = reinterpret_cast<const uint32_t*>(src)[q];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) fb |= (((wd >> (8 * j)) & 0xFFu) ? 1u : 0u) << (4 * q + j);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < PER; ++j) fb |= (src[j] ? 1u : 0u) << j;
+        }
+    }
+    if (a.seq) {
+        const uint32_t q = a.n_seq == 1 ? 0u : (uint32_t)(a.b_offset + x.b) % (uint32_t)a.n_seq;
+        const uint32_t* row = a.seq + (int64_t)q * a.Wc;
+#pragma unroll
+        for (int k = 0; k < NT; ++k) sm |= gold_bits(row, (int64_t)x.i * PER + k * QM, QM) << (k * QM);
+    }
+    fb ^= sm;
+    float xs[2 * NT], s[2 * NR], y[2 * NR];
+#pragma unroll
+    for (int k = 0; k < NT; ++k) {
+        uint32_t ci, cq;
+        qam_labels(H, [&](int i) { return ((fb >> (k * QM + i)) & 1u) != 0; }, ci, cq);
+        xs[2 * k] = qam_level(H, ci);
+        xs[2 * k + 1] = qam_level(H, cq);
+    }
+    mimo_apply<NT, NR>(h, xs, s);
+    const uint64_t Gre = (uint64_t)(a.first + loc);
+    const double sigma = (double)a.sigma;
+#pragma unroll
+    for (int q = 0; q < (NR + 1) / 2; ++q) {
+        const U4 c = mimo_counter(Gre, kMimoNoiseTag, (uint32_t)q, a.seed);
+        const double rad0 = sqrt(-2.0 * log(u01(c.x))), th0 = 6.283185307179586 * u01(c.y);
+        y[4 * q] = (float)((double)s[4 * q] + sigma * (rad0 * cos(th0)));
+        y[4 * q + 1] = (float)((double)s[4 * q + 1] + sigma * (rad0 * sin(th0)));
+        if (2 * q + 1 < NR) {
+            const double rad1 = sqrt(-2.0 * log(u01(c.z))), th1 = 6.283185307179586 * u01(c.w);
+            y[4 * q + 2] = (float)((double)s[4 * q + 2] + sigma * (rad1 * cos(th1)));
+            y[4 * q + 3] = (float)((double)s[4 * q + 3] + sigma * (rad1 * sin(th1)));
+        }
+    }
+    float* stage = mimo_stage<PERS>();
+    mimo_ml_store<H, NT, NR>(a, loc, h, y, sm, stage);
+    if (a.y_out) mimo_store_run<PERY>(a.y_out, loc, y, stage);
+}
+
+template <int H, int NT, int NR>
+static void mimo_ml_detect_host(float sigma, const float* y, const float* h, int64_t B, int64_t R, int32_t L,
+                                int32_t n_blk, float* llr) {
+    const float w = mimo_ml_weight(sigma);
+    for (int64_t loc = 0; loc < B * R; ++loc) {
+        const int64_t blk = mimo_block(mimo_index(loc, R, L), n_blk);
+        mimo_ml_detect<H, NT, NR>(h + blk * (2 * NR * NT), y + loc * (2 * NR), w, llr + loc * (NT * 2 * H));
+    }
+}
+
+// [qm / 2 - 1][mimo_dims_index]; nt = 4 stops at 16-QAM (mimo_ml_supported)
+#define NLDPC_MIMO_ML_LOW(K, H) {K<H, 1, 1>, K<H, 1, 2>, K<H, 1, 4>, K<H, 2, 2>, K<H, 2, 4>, K<H, 4, 4>}
+#define NLDPC_MIMO_ML_HIGH(K, H) {K<H, 1, 1>, K<H, 1, 2>, K<H, 1, 4>, K<H, 2, 2>, K<H, 2, 4>, nullptr}
+#define NLDPC_MIMO_ML_ORDERS(K) \
+    {NLDPC_MIMO_ML_LOW(K, 1), NLDPC_MIMO_ML_LOW(K, 2), NLDPC_MIMO_ML_HIGH(K, 3), NLDPC_MIMO_ML_HIGH(K, 4)}
+static const MimoKernel kMimoMlChannel[4][6] = NLDPC_MIMO_ML_ORDERS(mimo_ml_channel_kernel);
+static const MimoKernel kMimoMlDetect[4][6] = NLDPC_MIMO_ML_ORDERS(mimo_ml_detect_kernel);
+static const MimoHostDetect kMimoMlDetectHost[4][6] = NLDPC_MIMO_ML_ORDERS(mimo_ml_detect_host);
+#undef NLDPC_MIMO_ML_ORDERS
+#undef NLDPC_MIMO_ML_HIGH
+#undef NLDPC_MIMO_ML_LOW
+
+static int mimo_ml_order(const std::string& who, int32_t qm, int32_t nt) {
+    if (!mimo_ml_supported(qm, nt))
+        return fail(NLDPC_EUNSUPPORTED, who + ": nt = 4 is detected up to qm = 4 (64- and 256-QAM need a tree search)");
+    return NLDPC_OK;
+}
 }  // namespace nldpc
 
 using namespace nldpc;
@@ -471,4 +602,86 @@ extern "C" int nldpc_mimo_channel_llr(int32_t qm, int32_t method, int32_t nt, in
     a.scale = mimo_entry_scale(nt);
     a.seed = seed;
     return mimo_launch(who, kMimoChannel[qm / 2 - 1][method][mimo_dims_index(nt, nr)], a, a.total, stream);
+}
+
+extern "C" int nldpc_mimo_detect_ml_ref(int32_t qm, int32_t nt, int32_t nr, float sigma, const float* y, const float* h,
+                                        int64_t B, int64_t R, int64_t L, float* llr) {
+    const std::string who = "nldpc_mimo_detect_ml_ref";
+    if (int rc = mimo_demapper(who, qm, 0, sigma)) return rc;
+    if (int rc = mimo_dims(who, nt, nr)) return rc;
+    if (!y || !h || !llr || B <= 0 || R <= 0) return fail(NLDPC_EINVAL, who + ": bad argument");
+    if (R * nt * qm >= (int64_t)1 << 31 || R >= (int64_t)1 << 31 || B >= (int64_t)1 << 31)
+        return fail(NLDPC_EINVAL, who + ": B and R * nt * qm must be below 2^31");
+    MimoRows r{};
+    if (int rc = mimo_rows(who, B, R, L, r)) return rc;
+    if (int rc = mimo_ml_order(who, qm, nt)) return rc;
+    kMimoMlDetectHost[qm / 2 - 1][mimo_dims_index(nt, nr)](sigma, y, h, B, R, r.L, r.n_blk, llr);
+    return NLDPC_OK;
+}
+
+extern "C" int nldpc_mimo_detect_ml(int32_t qm, int32_t nt, int32_t nr, float sigma, const float* y, const float* h,
+                                    int64_t B, int64_t R, int64_t L, float* llr, void* stream) {
+    const std::string who = "nldpc_mimo_detect_ml";
+    if (int rc = mimo_demapper(who, qm, 0, sigma)) return rc;
+    if (int rc = mimo_dims(who, nt, nr)) return rc;
+    if (!y || !h || !llr || B <= 0 || R <= 0) return fail(NLDPC_EINVAL, who + ": bad argument");
+    if (R * nt * qm >= (int64_t)1 << 31 || R >= (int64_t)1 << 31) return fail(NLDPC_EINVAL, who + ": R * nt * qm must be below 2^31");
+    if (mimo_misaligned4(y) || mimo_misaligned4(h) || mimo_misaligned4(llr))
+        return fail(NLDPC_EINVAL, who + ": y, h and llr must be 4-byte aligned");
+    MimoArgs a{};
+    if (int rc = mimo_rows(who, B, R, L, a.r)) return rc;
+    if (int rc = mimo_ml_order(who, qm, nt)) return rc;
+    if (B >= (int64_t)1 << 31) return fail(NLDPC_EUNSUPPORTED, who + ": too large");
+    a.y_in = y;
+    a.h = h;
+    a.llr = llr;
+    a.total = B * R;
+    a.sigma = sigma;
+    return mimo_launch(who, kMimoMlDetect[qm / 2 - 1][mimo_dims_index(nt, nr)], a, a.total, stream);
+}
+
+extern "C" int nldpc_mimo_channel_llr_ml(int32_t qm, int32_t nt, int32_t nr, const uint8_t* f, int64_t B, int64_t E,
+                                         float sigma, uint64_t seed, int64_t b_offset, int64_t L, const float* h_in,
+                                         const uint32_t* seq, int64_t n_seq, float* llr, float* sym_out, float* h_out,
+                                         void* stream) {
+    const std::string who = "nldpc_mimo_channel_llr_ml";
+    if (int rc = mimo_demapper(who, qm, 0, sigma)) return rc;
+    if (int rc = mimo_dims(who, nt, nr)) return rc;
+    if (!llr || B <= 0 || E <= 0 || b_offset < 0) return fail(NLDPC_EINVAL, who + ": bad argument");
+    if (E >= (int64_t)1 << 31 || E % qm != 0) return fail(NLDPC_EINVAL, who + ": E must be below 2^31 and a multiple of qm");
+    if ((E / qm) % nt != 0) return fail(NLDPC_EINVAL, who + ": E / qm must be a multiple of nt");
+    if (mimo_misaligned4(llr) || mimo_misaligned4(sym_out) || mimo_misaligned4(h_in) || mimo_misaligned4(h_out))
+        return fail(NLDPC_EINVAL, who + ": llr, sym_out, h_in and h_out must be 4-byte aligned");
+    MimoArgs a{};
+    const int64_t R = E / qm / nt;
+    if (int rc = mimo_rows(who, B, R, L, a.r)) return rc;
+    if (h_in && h_out) {
+        const uintptr_t bytes = (uintptr_t)(B * a.r.n_blk) * (uintptr_t)(8 * nr * nt);
+        const uintptr_t i = reinterpret_cast<uintptr_t>(h_in), o = reinterpret_cast<uintptr_t>(h_out);
+        if (i < o + bytes && o < i + bytes) return fail(NLDPC_EINVAL, who + ": h_out must not overlap h_in");
+    }
+    if (seq) {
+        if (mimo_misaligned4(seq)) return fail(NLDPC_EINVAL, who + ": seq must be 4-byte aligned");
+        if (n_seq < 1) return fail(NLDPC_EINVAL, who + ": n_seq must be positive");
+    }
+    if (int rc = mimo_ml_order(who, qm, nt)) return rc;
+    if (B >= (int64_t)1 << 31 || b_offset >= (int64_t)1 << 31) return fail(NLDPC_EUNSUPPORTED, who + ": too large");
+    if (seq) {
+        a.seq = seq;
+        a.n_seq = n_seq;
+        a.Wc = (E + 31) >> 5;
+        if (n_seq >= (int64_t)1 << 31 || n_seq * a.Wc >= (int64_t)1 << 31) return fail(NLDPC_EUNSUPPORTED, who + ": too large");
+    }
+    a.f = f;
+    a.h = h_in;
+    a.llr = llr;
+    a.y_out = sym_out;
+    a.h_out = h_out;
+    a.total = B * R;
+    a.first = b_offset * R;
+    a.b_offset = b_offset;
+    a.sigma = sigma;
+    a.scale = mimo_entry_scale(nt);
+    a.seed = seed;
+    return mimo_launch(who, kMimoMlChannel[qm / 2 - 1][mimo_dims_index(nt, nr)], a, a.total, stream);
 }

@@ -12,7 +12,8 @@ Layers:
   nldpc.fading      flat block fading (Rician / Rayleigh, drawn or given gains) with perfect-CSI demapping for the QAM
                     channel, fused like modulation.qam_llr and bit-identical to it at unit gain
   nldpc.mimo        spatial multiplexing of one codeword over 1, 2 or 4 layers, an nr x nt flat block-fading channel and
-                    LMMSE soft detection in front of the demapper, fused like fading.qam_llr (TS 38.211 §6.3.1.3)
+                    LMMSE soft detection in front of the demapper, fused like fading.qam_llr (TS 38.211 §6.3.1.3); or
+                    exact max-log ML (joint) detection of the layers (detect_ml, qam_llr_ml)
   nldpc.crc         CRC attachment in front of the encoder, CRC checking and error accounting behind the decoder
                     (TS 38.212 §5.1)
   nldpc.transport   transport blocks: the TB CRC, code-block segmentation, per-block rate matching and concatenation,

@@ -40,7 +40,8 @@ EXPORTED = (
     "nldpc_fading_gain_ref", "nldpc_qam_demap_csi_ref", "nldpc_fading_gains", "nldpc_qam_demap_csi",
     "nldpc_qam_fading_channel_llr",
     "nldpc_mimo_entry_ref", "nldpc_mimo_filter_ref", "nldpc_mimo_detect_ref", "nldpc_mimo_channels", "nldpc_mimo_filter",
-    "nldpc_mimo_detect", "nldpc_mimo_channel_llr",
+    "nldpc_mimo_detect", "nldpc_mimo_channel_llr", "nldpc_mimo_detect_ml_ref", "nldpc_mimo_detect_ml",
+    "nldpc_mimo_channel_llr_ml",
 )
 
 
@@ -55,7 +56,8 @@ _ADDED_IN_ABI4 = ("nldpc_bce_loss_grad", "nldpc_bce_grad_unless_unit", "nldpc_co
                   "nldpc_qam_channel_llr_scrambled", "nldpc_fading_gain_ref", "nldpc_qam_demap_csi_ref",
                   "nldpc_fading_gains", "nldpc_qam_demap_csi", "nldpc_qam_fading_channel_llr", "nldpc_mimo_entry_ref",
                   "nldpc_mimo_filter_ref", "nldpc_mimo_detect_ref", "nldpc_mimo_channels", "nldpc_mimo_filter",
-                  "nldpc_mimo_detect", "nldpc_mimo_channel_llr")
+                  "nldpc_mimo_detect", "nldpc_mimo_channel_llr", "nldpc_mimo_detect_ml_ref", "nldpc_mimo_detect_ml",
+                  "nldpc_mimo_channel_llr_ml")
 
 
 class NldpcCfg(ctypes.Structure):
@@ -193,6 +195,12 @@ def _declare(lib):
         "nldpc_mimo_detect": (_i32, [_i32, _i32, _i32, _i32, ctypes.c_float, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
         "nldpc_mimo_channel_llr": (_i32, [_i32, _i32, _i32, _i32, _vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64,
                                           _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+        "nldpc_mimo_detect_ml_ref": (_i32, [_i32, _i32, _i32, ctypes.c_float, ctypes.POINTER(ctypes.c_float),
+                                            ctypes.POINTER(ctypes.c_float), _i64, _i64, _i64,
+                                            ctypes.POINTER(ctypes.c_float)]),
+        "nldpc_mimo_detect_ml": (_i32, [_i32, _i32, _i32, ctypes.c_float, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+        "nldpc_mimo_channel_llr_ml": (_i32, [_i32, _i32, _i32, _vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64,
+                                             _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
         "nldpc_awgn_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp]),
         "nldpc_channel_llr": (_i32, [_vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64, _i64, _i32, _vp, _i64, _i64,
                                      ctypes.c_float, _i64, _i64, ctypes.c_float, _vp]),

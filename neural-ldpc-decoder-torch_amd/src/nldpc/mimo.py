@@ -9,6 +9,9 @@ filter         a channel table -> the LMMSE filter W [B, n_blk, nt, nr, 2], the 
 detect         received samples [B, R, nr, 2] and a channel table -> LLRs [B, R*nt*qm] (nldpc_mimo_detect).
 qam_llr        the fused channel: bits -> (scramble) -> symbols -> H x -> AWGN -> filter -> equalise -> demap ->
                (descramble) in one kernel (nldpc_mimo_channel_llr), with drawn or given channels.
+detect_ml      the same inputs -> the exact max-log ML (joint) LLRs (nldpc_mimo_detect_ml): no Gaussian approximation
+               of the interference; two sliced passes of 2^(qm (nt - 1)) candidates per RE; nt = 4 up to qm = 4.
+qam_llr_ml     qam_llr with that detector (nldpc_mimo_channel_llr_ml): the same samples and channels, max-log only.
 sigma_for      Eb/N0 -> noise standard deviation per real dimension and receive antenna.
 
 A resource element (RE) carries nt consecutive symbols of a row, one per layer, so the layer mapping is the identity in
@@ -100,12 +103,8 @@ def filter(h: torch.Tensor, sigma: float):  # noqa: A001  (the name the stage ha
     return W, mu, w
 
 
-def detect(y: torch.Tensor, qm: int, sigma: float, h: torch.Tensor, *, L: int = 1, method: str = "maxlog",
-           out: torch.Tensor | None = None) -> torch.Tensor:
-    """fp32 [B, R*nt*qm] LLRs (> 0: bit 1) of the received samples y (contiguous fp32 [B, R, nr, 2] on the device) that
-    passed through the channels h (contiguous fp32 [B, n_blocks(R, L), nr, nt, 2]); sigma is the noise standard
-    deviation per real dimension and antenna.  method "maxlog" or "logmap"."""
-    qm, m, sigma, L = _order(qm), _method(method), _sigma(sigma), _length(L)
+def _samples(y, h):
+    """(B, R, nt, nr, device) of the received samples y [B, R, nr, 2] and a channel table h [., ., nr, nt, 2]"""
     dev = _device_of(y, "y")
     if y.dtype != torch.float32 or y.dim() != 4 or y.shape[3] != 2 or y.shape[0] < 1 or y.shape[1] < 1 or \
             not y.is_contiguous():
@@ -114,6 +113,16 @@ def detect(y: torch.Tensor, qm: int, sigma: float, h: torch.Tensor, *, L: int = 
     if not isinstance(h, torch.Tensor) or h.dim() != 5:
         raise ValueError("h must be a contiguous float32 [B, n_blk, nr, nt, 2] tensor")
     nt, nr = _dims(int(h.shape[3]), nr)
+    return B, R, nt, nr, dev
+
+
+def detect(y: torch.Tensor, qm: int, sigma: float, h: torch.Tensor, *, L: int = 1, method: str = "maxlog",
+           out: torch.Tensor | None = None) -> torch.Tensor:
+    """fp32 [B, R*nt*qm] LLRs (> 0: bit 1) of the received samples y (contiguous fp32 [B, R, nr, 2] on the device) that
+    passed through the channels h (contiguous fp32 [B, n_blocks(R, L), nr, nt, 2]); sigma is the noise standard
+    deviation per real dimension and antenna.  method "maxlog" or "logmap"."""
+    qm, m, sigma, L = _order(qm), _method(method), _sigma(sigma), _length(L)
+    B, R, nt, nr, dev = _samples(y, h)
     n_blk = n_blocks(R, L)
     if R * nt * qm >= 2 ** 31 or B * n_blk >= 2 ** 31:
         raise ValueError("R * nt * qm and B * n_blocks(R, L) must be below 2^31")
@@ -122,6 +131,24 @@ def detect(y: torch.Tensor, qm: int, sigma: float, h: torch.Tensor, *, L: int = 
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().nldpc_mimo_detect(qm, m, nt, nr, sigma, y.data_ptr(), h.data_ptr(), B, R, L,
                                                 out.data_ptr(), _lib.stream_of(dev)), "nldpc_mimo_detect")
+    return out
+
+
+def detect_ml(y: torch.Tensor, qm: int, sigma: float, h: torch.Tensor, *, L: int = 1,
+              out: torch.Tensor | None = None) -> torch.Tensor:
+    """fp32 [B, R*nt*qm] exact max-log ML LLRs (> 0: bit 1) of the received samples y and the channels h, both as
+    detect takes them: LLR(b) = (min_{x: b=0} |y - H x|^2 - min_{x: b=1} |y - H x|^2) / (2 sigma^2) over all 2^(qm nt)
+    symbol vectors of the resource element.  nt = 4 is detected up to qm = 4 (_lib.NldpcUnsupported beyond)."""
+    qm, sigma, L = _order(qm), _sigma(sigma), _length(L)
+    B, R, nt, nr, dev = _samples(y, h)
+    n_blk = n_blocks(R, L)
+    if R * nt * qm >= 2 ** 31 or B * n_blk >= 2 ** 31:
+        raise ValueError("R * nt * qm and B * n_blocks(R, L) must be below 2^31")
+    h = _table(h, (B, n_blk, nr, nt, 2), dev)
+    out = _out(out, (B, R * nt * qm), dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nldpc_mimo_detect_ml(qm, nt, nr, sigma, y.data_ptr(), h.data_ptr(), B, R, L,
+                                                   out.data_ptr(), _lib.stream_of(dev)), "nldpc_mimo_detect_ml")
     return out
 
 
@@ -139,7 +166,29 @@ def qam_llr(f: torch.Tensor | None, qm: int, sigma: float, *, nt: int, nr: int, 
     uses it.  return_symbols / return_channels: True (or a tensor to fill) also returns the received samples
     [B, R, nr, 2] / the channels; the result is then the tuple (llr[, samples][, channels]), and without scramble the
     LLRs are bit for bit detect(samples, qm, sigma, channels, L=L, method=method)."""
-    qm, m, sigma, L, (nt, nr) = _order(qm), _method(method), _sigma(sigma), _length(L), _dims(nt, nr)
+    qm, m = _order(qm), _method(method)
+    return _fused("nldpc_mimo_channel_llr", (qm, m), f, qm, sigma, nt, nr, L, h, B, E, seed, b_offset, scramble, device,
+                  out, return_symbols, return_channels)
+
+
+def qam_llr_ml(f: torch.Tensor | None, qm: int, sigma: float, *, nt: int, nr: int, L: int = 1,
+               h: torch.Tensor | None = None, B: int | None = None, E: int | None = None, seed: int = 2042,
+               b_offset: int = 0, scramble: torch.Tensor | None = None, device=None,
+               out: torch.Tensor | None = None, return_symbols: bool | torch.Tensor = False,
+               return_channels: bool | torch.Tensor = False):
+    """qam_llr with the exact max-log ML detector of detect_ml in place of the LMMSE one, in one kernel: the same
+    arguments without method, the same noise and channel streams, so the returned samples and channels are bit for bit
+    those of qam_llr, and without scramble the LLRs are bit for bit detect_ml(samples, qm, sigma, channels, L=L).
+    nt = 4 is detected up to qm = 4 (_lib.NldpcUnsupported beyond)."""
+    qm = _order(qm)
+    return _fused("nldpc_mimo_channel_llr_ml", (qm,), f, qm, sigma, nt, nr, L, h, B, E, seed, b_offset, scramble, device,
+                  out, return_symbols, return_channels)
+
+
+def _fused(entry, lead, f, qm, sigma, nt, nr, L, h, B, E, seed, b_offset, scramble, device, out, return_symbols,
+           return_channels):
+    """the argument checks and the call shared by the fused channels; lead = the entry's arguments before nt"""
+    sigma, L, (nt, nr) = _sigma(sigma), _length(L), _dims(nt, nr)
     if f is not None:
         dev, fB, fE = _bits(f, qm)
         if (B is not None and B != fB) or (E is not None and E != fE):
@@ -179,9 +228,8 @@ def qam_llr(f: torch.Tensor | None, qm: int, sigma: float, *, nt: int, nr: int, 
         n_seq = _seq_table(scramble, E)
         _on(dev, scramble)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nldpc_mimo_channel_llr(
-            qm, m, nt, nr, _lib.ptr(f), B, E, sigma, int(seed) & (2 ** 64 - 1), b_offset, L, _lib.ptr(h),
-            _lib.ptr(scramble), n_seq, out.data_ptr(), _lib.ptr(sym), _lib.ptr(h_out), _lib.stream_of(dev)),
-            "nldpc_mimo_channel_llr")
+        _lib.check(getattr(_lib.lib(), entry)(
+            *lead, nt, nr, _lib.ptr(f), B, E, sigma, int(seed) & (2 ** 64 - 1), b_offset, L, _lib.ptr(h),
+            _lib.ptr(scramble), n_seq, out.data_ptr(), _lib.ptr(sym), _lib.ptr(h_out), _lib.stream_of(dev)), entry)
     extra = tuple(t for t in (sym, h_out) if t is not None)
     return (out,) + extra if extra else out
